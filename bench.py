@@ -2,7 +2,7 @@
 """
 bench.py — headline benchmark of the MI355X hot path (contract: the round driver).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
         N > 1: one rank per GPU over RCCL — either already under `python -m torch.distributed.run --nproc-per-node N ...`
         (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in the environment), or typed plainly, in which case this process
         starts that launcher as a child before touching the GPU and relays rank 0's JSON line.
@@ -13,10 +13,17 @@ encoder) forward + backward + NT-Xent ('noise_contrastive') + SGD(lr .1, momentu
 Inputs are resident in HBM before the timed region.  N > 1: DistributedDataParallel over RCCL (gradient
 all-reduce inside the step), weak scaling (per-GPU batch fixed), value = clips of all ranks / max-over-ranks time.
 
-One JSON line on rank 0 with: the contract keys, `roofline` for the dominant kernel (the 64->64 3x3x3
-gather-GEMM, HIP events around its launches inside the timed steps), `cpu_baseline` (the CPU oracle timed on
-this host, bounded sample), and `secondary` (k-means embeddings/s at 100k x 512, K = 500 — the second half of
-BASELINE.json's metric — with its own roofline and CPU baseline).
+A plain run sets up, warms up, times the K steps and prints one JSON line on rank 0 with the contract keys
+(`value` clips/s, `ms_per_step` the wall time of one timed step).  --dump-outputs DIR: after the timed steps, rank 0
+writes what the last timed step computed as DIR/<name>.npy (see dump_outputs); inputs and initial weights are seeded,
+so two builds run with the same arguments can be compared array for array.
+
+--full adds everything else the line has carried: `roofline` for the dominant kernel (the 64->64 3x3x3 convolution,
+HIP events around its launches inside the timed steps; `traffic` from child rocprofv3 PMC passes), `whole_step`,
+`cpu_baseline` (the CPU oracle timed on this host, bounded sample), and `secondary` (k-means embeddings/s at
+100k x 512, K = 500 — the second half of BASELINE.json's metric — with its own roofline and CPU baseline; retrieval,
+memory-bank NCE, extraction and other training shapes).  --no-cpu-baseline / --no-secondary / --no-traffic / --quick
+trim a --full run.
 """
 import argparse
 import json
@@ -416,6 +423,37 @@ def nce_secondary():
                                    "(a dozen launches) is timed beside it"))
 
 
+DUMP_SAMPLE = 16384                  # elements per parameter / buffer tensor in the *_sample dumps
+
+
+def dump_outputs(out_dir, net, loss, emb):
+    """what the last timed step handed its caller, as float32 .npy files (~3 MB in all at R3D-18):
+    loss.npy (1,), embeddings.npy (B, out_dim) — the forward's output —, and the model after the SGD update as fixed seeded
+    samples of up to DUMP_SAMPLE elements per tensor, concatenated in state_dict order: params_sample.npy, grads_sample.npy
+    (the gradients that update used, same indices) and buffers_sample.npy (BatchNorm running statistics and batch counters)"""
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    sd = net.state_dict()                           # flushes the engines' pending num_batches_tracked bumps
+    pnames = dict(net.named_parameters())
+    rng = np.random.default_rng(0)
+    parts = dict(params_sample=[], grads_sample=[], buffers_sample=[])
+    for name, t in sd.items():
+        flat = t.detach().reshape(-1)
+        n = flat.numel()
+        idx = torch.from_numpy(np.sort(rng.choice(n, DUMP_SAMPLE, replace=False)) if n > DUMP_SAMPLE else np.arange(n)).to(flat.device)
+        if name in pnames:
+            g = pnames[name].grad
+            parts["params_sample"].append(flat[idx].float().cpu().numpy())
+            parts["grads_sample"].append(np.zeros(len(idx), np.float32) if g is None else g.detach().reshape(-1)[idx].float().cpu().numpy())
+        else:
+            parts["buffers_sample"].append(flat[idx].float().cpu().numpy())
+    arrays = dict(loss=np.array([float(loss.item())], np.float32), embeddings=emb.detach().float().cpu().numpy(),
+                  **{k: np.concatenate(v).astype(np.float32) for k, v in parts.items()})
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+    log(f"bench.py: wrote {', '.join(f'{k}.npy {tuple(v.shape)}' for k, v in arrays.items())} to {out_dir}")
+
+
 def self_launch(n):
     """`python bench.py --gpus N` typed plainly: start the N ranks as a CHILD `torch.distributed.run` (one process per GPU,
     rendezvous on 127.0.0.1) and relay rank 0's JSON line.  Nothing in this parent has touched the GPU yet (importing torch
@@ -455,13 +493,20 @@ def main():
     ap.add_argument("--steps", type=int, default=20)          # >= 20 timed steps ...
     ap.add_argument("--warmup", type=int, default=5)         # ... after >= 5 warm-up steps
     ap.add_argument("--batch", type=int, default=32, help="clips per GPU per step (16 anchors || 16 positives)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true")
-    ap.add_argument("--no-traffic", action="store_true", help="skip the child rocprofv3 --pmc passes that fill roofline.traffic")
-    ap.add_argument("--quick", action="store_true", help="secondary = the k-means row only (tests)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure roofline, whole-step FLOP rates, CPU baselines and the secondary rows (off: headline only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the secondary rows")
+    ap.add_argument("--no-traffic", action="store_true", help="--full: skip the child rocprofv3 --pmc passes that fill roofline.traffic")
+    ap.add_argument("--quick", action="store_true", help="--full: secondary = the k-means row only (tests)")
     ap.add_argument("--force-dist", action="store_true", help="init the process group / DDP / sharded k-means even at world size 1 (path test)")
     ap.add_argument("--self-launch", action="store_true", help="go through the child torch.distributed.run launcher even for --gpus 1 (path test)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    full = args.full
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -526,28 +571,32 @@ def main():
         opt.zero_grad(set_to_none=True)
         loss.backward()
         opt.step()
-        return loss
+        return loss, emb
 
     for _ in range(args.warmup):
         step()
-    # dominant kernel (largest share of a step's kernel time): conv_wino2p_kernel (round 6: the persistent form of conv_wino2_kernel) — Winograd F(4,3) along W x F(2,3) along H — on the 64->64
-    # 3x3x3 layers (layer1: 4 forward + 4 data-gradient launches per step, identical M x N x K).  Every such launch of the timed steps is
-    # bracketed with HIP events on the launch stream.  `roofline.achieved` / `frac` count the fp32 MFMA FLOPs the launch EXECUTES (a third of
-    # the direct form's 2 M N K) over its duration: a fraction of the pipe's peak, <= 1; the direct form's count is printed beside it.
-    eng = net._engine(x)
-    l1 = [p for (_, p1, p2, _) in eng.blocks[:2] for p in (p1, p2)]
-    for p in l1:
-        p.prof = []
+    if full:
+        # dominant kernel (largest share of a step's kernel time): conv_wino2p_kernel (round 6: the persistent form of conv_wino2_kernel) — Winograd F(4,3) along W x F(2,3) along H — on the 64->64
+        # 3x3x3 layers (layer1: 4 forward + 4 data-gradient launches per step, identical M x N x K).  Every such launch of the timed steps is
+        # bracketed with HIP events on the launch stream.  `roofline.achieved` / `frac` count the fp32 MFMA FLOPs the launch EXECUTES (a third of
+        # the direct form's 2 M N K) over its duration: a fraction of the pipe's peak, <= 1; the direct form's count is printed beside it.
+        eng = net._engine(x)
+        l1 = [p for (_, p1, p2, _) in eng.blocks[:2] for p in (p1, p2)]
+        for p in l1:
+            p.prof = []
     if world > 1:
         torch.distributed.barrier()
     torch.cuda.synchronize()
     t0 = time.time()
     for _ in range(args.steps):
-        loss = step()
+        loss, emb = step()
     torch.cuda.synchronize()
     if world > 1:
         torch.distributed.barrier()
     dt = time.time() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, net, loss, emb)
+    del emb
     dist_info = dict(initialised=bool(use_dist), world_size_env=world)
     if use_dist:
         # self-verification of a multi-GPU run: how many ranks RCCL really reduced over (a sum of ones), the library
@@ -573,6 +622,25 @@ def main():
         torch.distributed.all_reduce(tt, op=torch.distributed.ReduceOp.MAX)
         dt = float(tt.item())
     lossv = float(loss.item())
+    try:
+        metric_name = json.load(open(os.path.join(ROOT, "BASELINE.json")))["metric"]     # the exact string of BASELINE.json
+    except Exception:
+        metric_name = "clips/sec R3D-18+NCE (1/2/4/8 GPU); k-means embeddings/sec 100k\u00d7512"
+    res = dict(metric=metric_name,
+               value=world * B * args.steps / dt, unit="clips/s", n_gpus=world, steps=args.steps, warmup=args.warmup,
+               ms_per_step=dt / args.steps * 1e3, higher_is_better=True, scaling="weak", vs_baseline=None,
+               dtype="f32", data="synthetic", distributed=dist_info,
+               config=dict(workload="R3D-18 (3D-ResNet-18, 34.52 M params, no maxpool, 7^3 stem) fwd+bwd + NT-Xent "
+                                    "(noise_contrastive, T=0.5) + SGD(lr .1, mom .5); per-GPU batch "
+                                    f"{B} x 3x16x112x112 fp32 = {B//2} anchors || {B//2} positives; BASELINE configs[1]",
+                           global_batch=world * B, parallelism=f"dp{world}", final_loss=lossv))
+    if not full:
+        # a plain run: the headline and nothing else
+        if rank == 0:
+            print(json.dumps(res), flush=True)
+        if use_dist:
+            torch.distributed.destroy_process_group()
+        return
     # layer1's FORWARD launches: the same kernel, grid and K as its data-gradient launches, and nothing shares the GPU with them (the
     # backward's weight gradients run on a side stream beside the data gradients, so a data-gradient launch's duration describes two
     # kernels' share of the chip; it is reported beside the forward figure, not used for the roofline)
@@ -606,19 +674,7 @@ def main():
             except Exception:
                 pass
 
-    try:
-        metric_name = json.load(open(os.path.join(ROOT, "BASELINE.json")))["metric"]     # the exact string of BASELINE.json
-    except Exception:
-        metric_name = "clips/sec R3D-18+NCE (1/2/4/8 GPU); k-means embeddings/sec 100k\u00d7512"
-    res = dict(metric=metric_name,
-               value=world * B * args.steps / dt, unit="clips/s", n_gpus=world, steps=args.steps, warmup=args.warmup,
-               ms_per_step=dt / args.steps * 1e3, higher_is_better=True, scaling="weak", vs_baseline=None,
-               dtype="f32", data="synthetic", distributed=dist_info,
-               config=dict(workload="R3D-18 (3D-ResNet-18, 34.52 M params, no maxpool, 7^3 stem) fwd+bwd + NT-Xent "
-                                    "(noise_contrastive, T=0.5) + SGD(lr .1, mom .5); per-GPU batch "
-                                    f"{B} x 3x16x112x112 fp32 = {B//2} anchors || {B//2} positives; BASELINE configs[1]",
-                           global_batch=world * B, parallelism=f"dp{world}", final_loss=lossv),
-               roofline=dict(bound="mfma", achieved=ach, peak=FP32_MFMA_PEAK_TFLOPS, unit="TFLOP/s",
+    res.update(roofline=dict(bound="mfma", achieved=ach, peak=FP32_MFMA_PEAK_TFLOPS, unit="TFLOP/s",
                              frac=ach / FP32_MFMA_PEAK_TFLOPS, traffic=None, traffic_from_profile=traffic_prof,
                              traffic_source=traffic_src,
                              kernel=((("conv_wino2p_kernel<false> — the PERSISTENT form (256 workgroups walk the 3136 tile blocks; the next block's first DMAs are issued "

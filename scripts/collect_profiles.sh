@@ -6,8 +6,8 @@ R="$(pwd)"
 S="$R/gpurun_out/prof_r06"
 rm -rf "$S"; mkdir -p "$S"
 cd /tmp && export TMPDIR=/tmp
-timeout 600 python "$R/bench.py" > "$S/default.log" 2>&1 < /dev/null
-timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$S/stats" -- python "$R/bench.py" --steps 5 --warmup 2 --no-cpu-baseline --no-secondary > "$S/stats.log" 2>&1 < /dev/null
+timeout 600 python "$R/bench.py" --full > "$S/default.log" 2>&1 < /dev/null
+timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$S/stats" -- python "$R/bench.py" --full --steps 5 --warmup 2 --no-cpu-baseline --no-secondary > "$S/stats.log" 2>&1 < /dev/null
 timeout 400 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d "$S/pmc_fetch" -- python "$R/bench.py" --steps 2 --warmup 1 --no-cpu-baseline --no-secondary > "$S/pmc_fetch.log" 2>&1 < /dev/null
 timeout 400 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d "$S/pmc_write" -- python "$R/bench.py" --steps 2 --warmup 1 --no-cpu-baseline --no-secondary > "$S/pmc_write.log" 2>&1 < /dev/null
 timeout 400 rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY GRBM_GUI_ACTIVE --output-format csv -d "$S/pmc_sq" -- python "$R/bench.py" --steps 2 --warmup 1 --no-cpu-baseline --no-secondary > "$S/pmc_sq.log" 2>&1 < /dev/null
@@ -23,7 +23,7 @@ timeout 300 python "$R/scripts/bench_conv.py" 32 > "$S/conv_shapes.log" 2>&1 < /
 # round 5 rows: retrieval per kernel (collect vs streaming), the one-rank distributed path with the self-verifying fields and the one-shot
 # exchange row (stderr), the B = 8 step's kernel statistics, the planar-layout diagnostic of the dominant kernel
 (cd "$R" && timeout 300 bash scripts/r5/prof_topk.sh) > "$S/topk_kernels.log" 2>&1 < /dev/null
-timeout 400 python "$R/bench.py" --gpus 1 --force-dist --quick --no-cpu-baseline --steps 5 --warmup 2 > "$S/force_dist.log" 2> "$S/force_dist.err" < /dev/null
+timeout 400 python "$R/bench.py" --full --gpus 1 --force-dist --quick --no-cpu-baseline --steps 5 --warmup 2 > "$S/force_dist.log" 2> "$S/force_dist.err" < /dev/null
 grep '"row": "kmeans_oneshot"' "$S/force_dist.err" > "$S/force_dist_oneshot.json"
 (cd "$R" && timeout 300 bash scripts/r5/prof_b8.sh) > "$S/b8_kernels.log" 2>&1 < /dev/null
 # round 6 rows: the persistent kernel against the one-block kernel (per launch, per shape, whole steps), DistributedDataParallel at one rank

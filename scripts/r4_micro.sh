@@ -10,5 +10,5 @@ cat $O/table.txt
 export TMPDIR=/tmp
 rocprofv3 --pmc SQ_VALU_MFMA_COEXEC_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU --kernel-trace --output-format csv -d $O/pmc -- ./scripts/micro/mfma_valu_coexec pmc > $O/pmc_stdout.txt 2>&1 || echo "pmc pass failed"
 find $O/pmc -name "*counter_collection.csv" | head -1 | xargs -I{} cp {} $O/pmc_counters.csv
-python bench.py --no-cpu-baseline > $O/bench.json 2> $O/bench.err || exit 1
+python bench.py --full --no-cpu-baseline > $O/bench.json 2> $O/bench.err || exit 1
 tail -c 3000 $O/bench.json

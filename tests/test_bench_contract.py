@@ -1,6 +1,9 @@
-"""The JSON line bench.py prints (the copy kept under profiles/) carries every field the driver's contract names."""
+"""The JSON line bench.py prints (the copy kept under profiles/) carries every field the driver's contract names; a plain run
+prints the headline alone and --dump-outputs writes the last timed step's outputs."""
 import json
 import os
+
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -49,3 +52,43 @@ def test_bench_line_self_verifying_distributed_fields():
     assert sec["weak_scaled"]["scaling"] == "weak" and sec["weak_scaled"]["n_gpus"] == d["n_gpus"]
     one = d.get("kmeans_oneshot_row_from_stderr")
     assert one and one["exchange"]["kind"] == "oneshot" and one["value"] > 0
+
+
+def test_bench_cli_has_full_and_dump_outputs():
+    """--full (everything beyond the headline) and --dump-outputs DIR are options of the command line; parsing needs no GPU"""
+    import subprocess
+    import sys
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
+                       text=True, timeout=300)
+    assert p.returncode == 0, p.stdout[-2000:]
+    assert "--full" in p.stdout and "--dump-outputs DIR" in p.stdout
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_headline_and_dumped_outputs(gpu, tmp_path):
+    """a plain `bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR`: one JSON line with the headline keys and none of --full's
+    rows, K timed steps in ms_per_step, and the last step's outputs as float32 .npy files under 64 MB"""
+    import subprocess
+    import sys
+    import numpy as np
+    out = tmp_path / "dump"
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(out)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-4000:]
+    lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, p.stdout[-2000:]
+    d = json.loads(lines[0])
+    base = json.load(open(os.path.join(ROOT, "BASELINE.json")))
+    assert d["metric"] == base["metric"] and d["unit"] == "clips/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0
+    assert abs(d["value"] - d["config"]["global_batch"] / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+    for k in ("roofline", "whole_step", "cpu_baseline", "secondary"):
+        assert k not in d, k
+    files = {f: np.load(os.path.join(out, f)) for f in os.listdir(out)}
+    assert set(files) == {"loss.npy", "embeddings.npy", "params_sample.npy", "grads_sample.npy", "buffers_sample.npy"}
+    assert sum(os.path.getsize(os.path.join(out, f)) for f in files) <= 64 << 20
+    for f, a in files.items():
+        assert a.dtype in (np.float32, np.float64) and a.size > 0 and np.isfinite(a).all(), f
+    assert files["embeddings.npy"].shape == (32, 128)
+    assert abs(float(files["loss.npy"][0]) - d["config"]["final_loss"]) <= 1e-6 * max(1.0, abs(d["config"]["final_loss"]))
+    assert files["params_sample.npy"].shape == files["grads_sample.npy"].shape

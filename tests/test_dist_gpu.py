@@ -269,7 +269,7 @@ def test_bench_self_launch_one_rank(gpu):
     """`python bench.py --gpus N` typed plainly starts its own torch.distributed.run child (before any GPU call in the
     parent) and relays rank 0's JSON line: exercised with N = 1 (+ --force-dist: DDP and the sharded k-means over a
     one-rank RCCL group), the same code path the driver takes for N = 2, 4, 8"""
-    r = _bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--self-launch", "--force-dist", "--no-cpu-baseline", "--quick"])
+    r = _bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--self-launch", "--force-dist", "--full", "--no-cpu-baseline", "--quick"])
     assert r["n_gpus"] == 1 and r["steps"] == 2 and r["value"] > 0 and r["config"]["parallelism"] == "dp1"
     assert "sharded" in r["secondary"]["config"]["workload"]
     # the fields that make a multi-GPU run self-verifying (what RCCL really reduced over, not what WORLD_SIZE claims)
@@ -286,6 +286,6 @@ def test_bench_self_launch_one_rank(gpu):
 
 @pytest.mark.skipif(torch.cuda.device_count() < 2, reason="needs two GPUs")
 def test_bench_two_gpus_plain_invocation(gpu):
-    r = _bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--quick"])
+    r = _bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--quick"])
     assert r["n_gpus"] == 2 and r["config"]["global_batch"] == 64 and r["scaling"] == "weak"
     assert r["secondary"]["n_gpus"] == 2 and r["distributed"]["rccl_ranks_seen"] == 2 and len(r["distributed"]["ms_per_step_per_rank"]) == 2
