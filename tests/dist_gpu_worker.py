@@ -137,6 +137,171 @@ def case_ddp_fast(rank, world, out):
              nbt=int(sd_after["bn1.num_batches_tracked"].item()))
 
 
+class _RecordingSGD:
+    """SGD-momentum that records every step's gradients and the weights after it; `mean_over` = the world size of an un-wrapped model, whose
+    gradients are averaged over the ranks first (what DistributedDataParallel is specified to produce)"""
+
+    def __init__(self, params, mean_over=None):
+        self.params = list(params)
+        self.opt = torch.optim.SGD(self.params, lr=0.05, momentum=0.5)
+        self.mean_over = mean_over
+        self.grads, self.weights = [], []
+
+    def zero_grad(self, set_to_none=True):
+        self.opt.zero_grad(set_to_none=set_to_none)
+
+    def step(self):
+        if self.mean_over is not None:
+            for p in self.params:
+                dist.all_reduce(p.grad)
+                p.grad.div_(self.mean_over)
+        self.grads.append([p.grad.clone() for p in self.params])
+        self.opt.step()
+        self.weights.append([p.detach().clone() for p in self.params])
+
+
+class _SyncedBuffers(torch.nn.Module):
+    """the un-wrapped model with DistributedDataParallel's buffer rule: rank 0's buffers before every forward"""
+
+    def __init__(self, net):
+        super().__init__()
+        self.net = net
+
+    def forward(self, *xs):
+        for b in self.net.buffers():
+            dist.broadcast(b, 0)
+        return self.net(*xs)
+
+
+def _count_view_writes():
+    """wraps models.resnet._grad_out: returns a list that receives every parameter whose gradient went into a handed-over bucket view"""
+    from video_similarity_search_amd.models import resnet as rn
+    inner, writes = rn._grad_out, []
+
+    def counted(p):
+        gv = rn._GRAD_VIEWS[0]
+        v = gv.get(p) if gv else None
+        g = inner(p)
+        if v is not None and g.untyped_storage().data_ptr() == v.untyped_storage().data_ptr():
+            writes.append(p)
+        return g
+
+    rn._grad_out = counted
+    return writes
+
+
+def _ddp_fast_pattern(rank, world, out, pattern):
+    """data_parallel under the backward patterns besides the headline's (one forward, zero_grad after it), four steps each: gradients and
+    the weights after every SGD step bit-equal to the un-wrapped model with an explicit gradient mean over the ranks (as case_ddp_fast).
+    two_fwd: contrastive_train_epoch itself (two forwards, the fused NCE step, zero_grad, backward); three_fwd: Tripletnet's three passes
+    in one forward; zero_not_none: zero_grad(set_to_none=False) before the backward; no_sync: two micro-batches under no_sync(), then a
+    synced third; zero_before_fwd: zero_grad() before the forward.  Also records how many gradients went into bucket views per step."""
+    import types
+    from video_similarity_search_amd import online_train
+    from video_similarity_search_amd.loss import OnlineTripletLoss, NCEAverage, NCESoftmaxLoss
+    from video_similarity_search_amd.misc.distributed_helper import data_parallel
+    from video_similarity_search_amd.models import Tripletnet
+    writes = _count_view_writes()
+    m, sd0 = tiny_state_dict()
+    m = m.cuda().train()
+    ref, _ = tiny_state_dict()
+    ref.load_state_dict(sd0)
+    ref = ref.cuda().train()
+    net_d, net_r = (Tripletnet(m, 'cosine'), Tripletnet(ref, 'cosine')) if pattern == "three_fwd" else (m, ref)
+    ddp = data_parallel(net_d, torch.cuda.current_device())
+    ref_s = _SyncedBuffers(net_r)
+    opt_d = _RecordingSGD(ddp.parameters())
+    opt_r = _RecordingSGD(net_r.parameters(), mean_over=world)
+    crit = OnlineTripletLoss(0.2, 'cosine')
+    labels = torch.arange(2).repeat(2).cuda()
+    steps = 4
+
+    def clip(step, k):
+        rng = np.random.default_rng(1000 * step + 10 * k + rank)                # every rank, step and pass its own clips
+        return torch.from_numpy(rng.standard_normal((4, 3, 8, 32, 32)).astype(np.float32)).cuda()
+
+    def loss_of(net, x):
+        return crit(net(x), labels, sampling_strategy='noise_contrastive')[0]
+
+    written = []
+    if pattern == "two_fwd":
+        cfg = types.SimpleNamespace(NUM_GPUS=world, TRAIN=types.SimpleNamespace(LOG_INTERVAL=10 ** 9), OUTPUT_PATH=None)
+        loader = [([clip(s, 0)], torch.zeros(4, dtype=torch.long), torch.arange(4) + 4 * s + 16 * rank) for s in range(steps)]
+        banks = []
+        for net, opt in ((ref_s, opt_r), (ddp, opt_d)):
+            torch.manual_seed(21)                                                   # the same memory banks on both sides
+            contrast = NCEAverage(32, 64, 16, 0.07, 0.5).cuda()
+            torch.cuda.manual_seed(5 + rank)                                        # the same negatives drawn
+            n0 = len(writes)
+            online_train.contrastive_train_epoch(loader, net, NCESoftmaxLoss(), NCESoftmaxLoss(), contrast, opt, 0, cfg, True, "cuda",
+                                                 is_master_proc=False)
+            written.append(len(writes) - n0)                                        # (the whole epoch: the un-wrapped side writes none)
+            banks.append(contrast.memory_l.clone())
+        banks_equal = torch.equal(banks[0], banks[1])
+    else:
+        banks_equal = True
+        margin = torch.nn.MarginRankingLoss(margin=0.2)
+        for step in range(steps):
+            for net, opt, wrapped in ((ref_s, opt_r, False), (ddp, opt_d, True)):
+                n0 = len(writes)
+                if pattern == "three_fwd":
+                    da, db = net(clip(step, 0), clip(step, 1), clip(step, 2))[:2]
+                    loss = margin(da, db, -torch.ones_like(da))
+                    opt.zero_grad()
+                    loss.backward()
+                elif pattern == "zero_not_none":
+                    loss = loss_of(net, clip(step, 0))
+                    opt.zero_grad(set_to_none=False)
+                    loss.backward()
+                elif pattern == "no_sync":
+                    if wrapped:
+                        with ddp.no_sync():
+                            loss = loss_of(ddp, clip(step, 0))
+                            opt.zero_grad()
+                            loss.backward()
+                            loss_of(ddp, clip(step, 1)).backward()
+                    else:                                   # under no_sync() the wrapper broadcasts its buffers before the first micro-batch only
+                        loss = loss_of(ref_s, clip(step, 0))
+                        opt.zero_grad()
+                        loss.backward()
+                        loss_of(net_r, clip(step, 1)).backward()
+                    loss_of(net_r if not wrapped else ddp, clip(step, 2)).backward()
+                elif pattern == "zero_before_fwd":
+                    opt.zero_grad()
+                    loss_of(net, clip(step, 0)).backward()
+                else:
+                    raise ValueError(pattern)
+                opt.step()
+                if wrapped:
+                    written.append(len(writes) - n0)
+    nbad = sum(int(not torch.equal(a, b)) for gd, gr in zip(opt_d.grads, opt_r.grads) for a, b in zip(gd, gr))
+    nbad_w = sum(int(not torch.equal(a, b)) for wd, wr in zip(opt_d.weights, opt_r.weights) for a, b in zip(wd, wr))
+    worst = max(float((a - b).abs().max().item()) for gd, gr in zip(opt_d.grads, opt_r.grads) for a, b in zip(gd, gr))
+    np.savez(out, n_steps=len(opt_d.grads), n_steps_ref=len(opt_r.grads), n_params=len(opt_d.params), n_grad_not_equal=nbad,
+             n_weight_not_equal=nbad_w, worst_abs=worst, written=np.array(written), banks_equal=banks_equal,
+             bufs_equal_ref=all(torch.equal(a, b) for a, b in zip(net_d.buffers(), net_r.buffers())))
+
+
+def case_ddp_fast_two_fwd(rank, world, out):
+    _ddp_fast_pattern(rank, world, out, "two_fwd")
+
+
+def case_ddp_fast_three_fwd(rank, world, out):
+    _ddp_fast_pattern(rank, world, out, "three_fwd")
+
+
+def case_ddp_fast_zero_not_none(rank, world, out):
+    _ddp_fast_pattern(rank, world, out, "zero_not_none")
+
+
+def case_ddp_fast_no_sync(rank, world, out):
+    _ddp_fast_pattern(rank, world, out, "no_sync")
+
+
+def case_ddp_fast_zero_before_fwd(rank, world, out):
+    _ddp_fast_pattern(rank, world, out, "zero_before_fwd")
+
+
 def case_kmeans(rank, world, out):
     """KMeans(process_group=WORLD) on the HIP kernels: rows sharded, slic_kmeans_lloyd_local -> ONE collective over RCCL (fp64
     all-reduce of [sums | counts | n_changed], or all-gather of the fp32 payloads) -> slic_kmeans_lloyd_global; explicit init

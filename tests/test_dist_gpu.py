@@ -74,6 +74,28 @@ def test_data_parallel_fast_wrapper_equals_plain_steps(gpu, tmp_path, world):
         assert al[0] == 0 and al[2] == 66 and al[3] == 66, al          # step 1: nothing handed over yet; step 2: views of the first buckets (rebuilt since)
 
 
+@pytest.mark.parametrize("pattern", ["two_fwd", "three_fwd", "zero_not_none", "no_sync", "zero_before_fwd"])
+@pytest.mark.parametrize("world", _worlds())
+def test_data_parallel_fast_wrapper_backward_patterns(gpu, tmp_path, world, pattern):
+    """data_parallel's bucket views under every other backward pattern of a training loop — contrastive_train_epoch's two forwards,
+    Tripletnet's three passes, zero_grad(set_to_none=False), no_sync() accumulation, zero_grad() before the forward: four steps of
+    gradients and weights bit-equal to the un-wrapped model with an explicit gradient mean (a view written twice, or over an accumulated
+    .grad, doubles gradients instead)"""
+    res = _run("ddp_fast_" + pattern, world, tmp_path)
+    for r in res:
+        assert int(r["n_params"]) == 66 and int(r["n_steps"]) == int(r["n_steps_ref"]) == 4
+        assert int(r["n_grad_not_equal"]) == 0, float(r["worst_abs"])
+        assert int(r["n_weight_not_equal"]) == 0
+        assert bool(r["bufs_equal_ref"]) and bool(r["banks_equal"])
+        wr = [int(v) for v in r["written"]]
+        if pattern == "two_fwd":
+            assert wr[0] == 0 and wr[1] <= 66 * 4, wr                 # (whole epochs: un-wrapped, wrapped) — one view per parameter and step
+        elif pattern == "zero_before_fwd":
+            assert wr == [0] * 4, wr                                   # .grad is None at every forward: nothing is handed over
+        else:
+            assert all(0 <= v <= 66 for v in wr), wr
+
+
 @pytest.mark.parametrize("world", _worlds())
 def test_sync_batchnorm_equals_full_batch(gpu, tmp_path, world):
     """cfg.SYNC_BATCH_NORM (online_train.py:466-468): SyncBatchNorm over W ranks with B / W clips each == plain BatchNorm over

@@ -1002,6 +1002,60 @@ def test_tiny_encoder_ragged_sizes_vs_oracle(gpu, shape):
         assert d_gpu <= max(1e-3, 3 * d_cpu), (k, d_gpu, d_cpu)
 
 
+@pytest.mark.parametrize("case", ["two_passes", "three_passes", "two_batch_sizes", "two_backwards"])
+def test_tiny_encoder_multi_pass_gradients_vs_oracle(gpu, case):
+    """several train-mode passes of ONE module per step, gradients against the fp64 oracle (the fused-vs-unfused test above only compares
+    the engine with itself): two and three live passes under a loss that mixes them (contrastive_train_epoch's two views, Tripletnet's
+    three); two live passes at different batch sizes (two engines of the module alive at once); two backward calls with no zeroing in
+    between (the accumulated .grad against the fp64 sum of both losses' gradients)"""
+    from oracle import encoder as oe
+    from video_similarity_search_amd.models import generate_model
+    from video_similarity_search_amd.loss.triplet_loss import ntxent_loss
+    rng = np.random.default_rng(41)
+    sd = oe.make_state_dict(rng, widen=0.125, hidden=64, out_dim=32)
+    sizes = {"two_passes": (4, 4), "three_passes": (4, 4, 4), "two_batch_sizes": (4, 6), "two_backwards": (4, 4)}[case]
+    xs = [torch.from_numpy(rng.standard_normal((B, 3, 8, 32, 32)).astype(np.float32)) for B in sizes]
+    m = generate_model(18, **dict(R3D18_KW, widen_factor=0.125, hidden_layer=64, out_dim=32))
+    _load_into(m, sd)
+    m = m.cuda().train()
+    names = ["conv1.weight", "layer2.0.conv1.weight", "layer3.0.downsample.0.weight", "layer4.1.conv2.weight", "fc1.weight"]
+
+    def losses(embs, ntx):
+        # one loss over all live passes, or (two_backwards) one per pass, the second scaled so that the two terms differ
+        if case == "two_backwards":
+            return [ntx(embs[0]), 0.5 * ntx(embs[1])]
+        return [ntx(torch.cat(embs))]
+
+    if case == "two_backwards":
+        embs = []
+        for i, x in enumerate(xs):
+            embs.append(m(x.cuda()))
+            ((0.5 if i else 1.0) * ntxent_loss(embs[-1])).backward()             # .grad accumulates across the two calls
+        assert len(m._engines) == 1
+    else:
+        embs = [m(x.cuda()) for x in xs]
+        losses(embs, ntxent_loss)[0].backward()
+        assert len(m._engines) == len(set(sizes))
+    ref = {}
+    for dt in (torch.float64, torch.float32):
+        t = oe.to_torch(sd, dtype=dt, requires_grad=True)
+        e = [oe.encoder_forward(t, x.to(dt), training=True) for x in xs]
+        g = [torch.zeros_like(t[k]) for k in names]
+        for l in losses(e, oe.ntxent_loss):
+            g = [a + b for a, b in zip(g, torch.autograd.grad(l, [t[k] for k in names]))]
+        ref[dt] = (e, g)
+    for e_gpu, e64 in zip(embs, ref[torch.float64][0]):
+        assert (e_gpu.detach().cpu().double() - e64.detach()).abs().max().item() <= 1e-4
+    pd = dict(m.named_parameters())
+    # the gate of test_tiny_encoder_ragged_sizes_vs_oracle: 1e-3 of the tensor's largest entry against fp64, or three times the fp32 CPU
+    # oracle's own distance where that is larger — a pass's gradient lost, doubled or overwritten moves whole tensors by O(1)
+    for k, g64, g32 in zip(names, ref[torch.float64][1], ref[torch.float32][1]):
+        scale = g64.abs().max().clamp_min(1e-30).item()
+        d_gpu = (pd[k].grad.cpu().double() - g64).abs().max().item() / scale
+        d_cpu = (g32.double() - g64).abs().max().item() / scale
+        assert d_gpu <= max(1e-3, 3 * d_cpu), (k, d_gpu, d_cpu)
+
+
 def test_config0_r3d18_eval_forward_b2_vs_oracle(gpu):
     """BASELINE configs[0]: R3D-18 forward on one synthetic 2 x 3 x 16 x 112 x 112 batch (eval mode, so the BatchNorm1d of the
     head uses its running statistics and B = 2 is well posed) vs the CPU oracle (models/resnet.py:255-312), 1e-4"""

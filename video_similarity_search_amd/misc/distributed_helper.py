@@ -85,11 +85,16 @@ def get_world_size():
 #   * buffers: the BatchNorm running statistics (and their int64 counters) are re-pointed into ONE flat tensor per dtype — the
 #     registered buffers, their names and state_dict keys stay — DistributedDataParallel is told to leave them alone, and a forward
 #     pre-hook broadcasts the flat tensors from rank 0: two collectives per forward, no flatten / unflatten copies (same semantics
-#     as broadcast_buffers=True: rank 0's statistics win before every forward);
-#   * gradients: with gradient_as_bucket_view the engine writes every weight gradient STRAIGHT into the parameter's bucket view (the
+#     as broadcast_buffers=True: rank 0's statistics win before every forward that follows a synced training forward);
+#   * gradients: with gradient_as_bucket_view the engine writes a weight gradient STRAIGHT into the parameter's bucket view (the
 #     view a parameter's .grad held after the previous step, handed to the engine before each forward): autograd installs it as .grad,
-#     DistributedDataParallel finds it aliasing its bucket and copies nothing (a view gone stale — buckets rebuilt, .grad replaced by
-#     the user — is just another tensor: the copy happens as before);
+#     DistributedDataParallel finds it aliasing its bucket and copies nothing.  That happens when the step is one forward and .grad is
+#     None when the backward reaches the parameter (zero_grad() with set_to_none=True after the forward: the reference's order).  In
+#     every other case the gradient goes to a new tensor and the reducer copies it as the plain wrapper does: a view is used at most
+#     once per backward, so with several forwards per backward (contrastive_train_epoch's two, Tripletnet's three) only one pass writes
+#     it and autograd adds the other passes' gradients to it; a .grad still present at backward time (zero_grad(set_to_none=False),
+#     gradient accumulation, no_sync()) is accumulated into, never overwritten; zero_grad() before the forward leaves nothing to hand
+#     over; a view gone stale (buckets rebuilt, .grad replaced by the user) is just another tensor;
 #   * the 1 / world scale: one all-reduce with ReduceOp.AVG per bucket as the communication hook instead of a division per parameter.
 # ------------------------------------------------------------------------------------------------------------------------------
 def _flatten_buffers(module):
@@ -118,6 +123,18 @@ def _flatten_buffers(module):
     return flats, names
 
 
+def _unflatten_buffers(module, names):
+    """undo _flatten_buffers and the ignore list: every named buffer gets storage of its own again (values kept)"""
+    names = set(names)
+    for name, buf in module.named_buffers():
+        if name in names:
+            buf.data = buf.detach().clone()
+            if hasattr(buf, "_ddp_ignored"):
+                del buf._ddp_ignored
+    if hasattr(module, "_ddp_params_and_buffers_to_ignore"):
+        del module._ddp_params_and_buffers_to_ignore
+
+
 def data_parallel(model, device=None, process_group=None, broadcast_buffers=True, bucket_cap_mb=25, **ddp_kwargs):
     """DistributedDataParallel(module=model, device_ids=[device]) for a model of this package, without the wrapper's per-step copies
     (see above).  Returns the DistributedDataParallel instance; `.slic_ddp` on it says what was set up."""
@@ -137,8 +154,6 @@ def data_parallel(model, device=None, process_group=None, broadcast_buffers=True
         for mod in model.modules():                      # plans cache nothing of the buffers, but an engine built before the re-pointing is dropped anyway
             if hasattr(mod, "_engines"):
                 mod._engines = {}
-    ddp = DDP(model, device_ids=[device] if on_gpu else None, process_group=pg, broadcast_buffers=broadcast_buffers, gradient_as_bucket_view=True,
-              bucket_cap_mb=bucket_cap_mb, **ddp_kwargs)      # (a CPU model over gloo — tests — takes the same route; ReduceOp.AVG is RCCL's: gloo keeps the default scale)
     world = torch.distributed.get_world_size(pg)
 
     def avg_hook(group, bucket):
@@ -152,10 +167,18 @@ def data_parallel(model, device=None, process_group=None, broadcast_buffers=True
         fut.set_result(bucket.buffer())
         return fut
 
-    if torch.distributed.get_backend(pg) == "nccl":
-        ddp.register_comm_hook(pg, identity_hook if world == 1 else avg_hook)
-        info["scale"] = ("none needed: one rank (identity hook, no collective)" if world == 1 else
-                         "ReduceOp.AVG inside the bucket's all-reduce (communication hook)")
+    try:
+        ddp = DDP(model, device_ids=[device] if on_gpu else None, process_group=pg, broadcast_buffers=broadcast_buffers, gradient_as_bucket_view=True,
+                  bucket_cap_mb=bucket_cap_mb, **ddp_kwargs)  # (a CPU model over gloo — tests — takes the same route; ReduceOp.AVG is RCCL's: gloo keeps the default scale)
+        if torch.distributed.get_backend(pg) == "nccl":
+            ddp.register_comm_hook(pg, identity_hook if world == 1 else avg_hook)
+            info["scale"] = ("none needed: one rank (identity hook, no collective)" if world == 1 else
+                             "ReduceOp.AVG inside the bucket's all-reduce (communication hook)")
+    except BaseException:
+        # leave the model as it came: a plain DistributedDataParallel built on it next (bench.py's fallback) must see its buffers and
+        # broadcast them
+        _unflatten_buffers(model, names)
+        raise
     views = {}
     for mod in model.modules():
         if hasattr(mod, "_engines"):
@@ -163,17 +186,25 @@ def data_parallel(model, device=None, process_group=None, broadcast_buffers=True
     info["gradient_into_bucket_views"] = True
     params = [p for p in model.parameters() if p.requires_grad]
 
-    def pre_forward(_mod, _args):
-        # (1) rank 0's statistics to everyone: what broadcast_buffers=True does, as one collective per dtype and no copies
-        if flats and (world > 1 or os.environ.get("SLIC_DDP_BROADCAST_AT_ONE_RANK", "0") != "0"):
+    known = {}               # parameter -> the last bucket view its .grad was (the engine's write leaves .grad an alias of it that is no view)
+
+    def pre_forward(mod, _args):
+        # (1) rank 0's statistics to everyone: what broadcast_buffers=True does, as one collective per dtype and no copies.  The wrapper
+        # syncs its buffers only if the previous forward ran with gradients and outside no_sync() (require_forward_param_sync): same rule
+        if flats and getattr(mod, "require_forward_param_sync", True) and (world > 1 or os.environ.get("SLIC_DDP_BROADCAST_AT_ONE_RANK", "0") != "0"):
             for f in flats:
                 torch.distributed.broadcast(f, src=torch.distributed.get_global_rank(pg, 0) if hasattr(torch.distributed, "get_global_rank") else 0,
                                             group=pg)
-        # (2) the bucket views the gradients of the previous step live in: the engine writes the next gradients there
+        # (2) the bucket views the gradients of the previous step live in: the engine writes the next gradients there (models/resnet.py:
+        # _grad_out takes each out of the dict when it uses it, and only while .grad is None)
         for p in params:
             g = p.grad
-            if g is not None and g._is_view() and g.is_contiguous() and g.shape == p.shape:
-                views[p] = g
+            if g is None or not g.is_contiguous() or g.shape != p.shape:
+                continue
+            if g._is_view():
+                known[p] = views[p] = g
+            elif p in known and g.data_ptr() == known[p].data_ptr():
+                views[p] = known[p]
         return None
 
     ddp.register_forward_pre_hook(pre_forward)

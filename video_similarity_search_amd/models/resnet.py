@@ -109,11 +109,14 @@ _GRAD_VIEWS = [None]       # the pass's {parameter: DistributedDataParallel buck
 def _grad_out(p):
     """where the gradient of parameter p is written: a FRESH alias of its DistributedDataParallel bucket view when one was handed over
     (autograd installs a gradient nobody else references as .grad without a copy; the reducer then finds .grad aliasing its bucket and
-    copies nothing), else a new tensor"""
+    copies nothing), else a new tensor.  A view is taken out of the dict, so it is written at most once per backward — with several live
+    passes (Tripletnet, two views of a clip) only one of them lands there, and autograd sums it with the others' new tensors — and only
+    while p.grad is None: a .grad that is still the view (zero_grad(set_to_none=False), gradient accumulation, no_sync()) is what
+    AccumulateGrad adds into, so the new gradient must not overwrite it"""
     gv = _GRAD_VIEWS[0]
     if gv:
-        v = gv.get(p)
-        if v is not None and v.shape == p.shape and v.device == p.device and v.dtype == p.dtype:
+        v = gv.pop(p, None)
+        if v is not None and p.grad is None and v.shape == p.shape and v.device == p.device and v.dtype == p.dtype:
             return v.detach()
     return torch.empty_like(p, memory_format=torch.contiguous_format)
 
