@@ -552,6 +552,15 @@ int slic_cosine_topk(const float* Qn, int Nq, const float* Gn, int Ng, int D, in
  * sharded by rows across GPUs */
 int slic_topk_merge_lists(const float* pdist, const int32_t* pidx, int W, int Nq, int k, int32_t* out_idx,
                           float* out_dist, void* stream);
+/* Euclidean top-k retrieval (LOSS.DIST_METRIC 'euclidean': validation.py:81,130, evaluate.py:367): for every row of Q the k nearest
+ * rows of G by |q - g|_2, ascending (ties -> lower gallery index); self_mask as above.  Q [Nq, D] (row stride ldq), G [Ng, D] (ldg): raw
+ * rows, any D; the library centres both on G's column mean and pads D to a multiple of 8 in its workspace.  The cosine path's kernels rank
+ * the k + 8 (at most 88, at most Ng) best rows by q.g - |g|^2 / 2, then the distances of those rows are recomputed directly from the raw
+ * rows in float64 and the k nearest are kept: exact duplicates come back at 0.  Limits as slic_cosine_topk (1 <= k <= min(88, Ng);
+ * SLIC_EINVAL beyond).  The path choice is slic_cosine_topk_plan(Nq, Ng, D rounded up to 8, that list length), SLIC_TOPK_COLLECT alike. */
+size_t slic_euclidean_topk_workspace_bytes(int Nq, int Ng, int D, int k);
+int slic_euclidean_topk(const float* Q, int Nq, int ldq, const float* G, int Ng, int ldg, int D, int k, int self_mask,
+                        int32_t* out_idx, float* out_dist, void* workspace, void* stream);
 /* euclidean_distances(X, Y) as a dense [Nx, Ny] matrix (evaluate.py:216; validation-size inputs) */
 int slic_pairwise_euclidean(const float* X, int Nx, const float* Y, int Ny, int D, float* out, void* stream);
 

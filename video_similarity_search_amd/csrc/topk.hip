@@ -12,6 +12,7 @@
 // A candidate replaces the root and sifts down: O(log k) per insertion, O(k log(Ng/k)) insertions per query and slice in
 // expectation.  Order: larger s first, ties -> lower gallery index.
 // slic_topk_merge folds the per-slice lists into the final sorted [Nq, k].
+// The same kernels serve euclidean top-k (slic_euclidean_topk, at the end of this file) through their EU instantiations.
 #include "common.h"
 #include <math.h>
 #include <limits.h>
@@ -45,9 +46,14 @@ __device__ __forceinline__ bool tk_better(float s, int i, float t, int ti) {
   return s > t || (s == t && i < ti);
 }
 
+// EU (every partial / collect kernel below): the euclidean ranking score s = q.g - |g|^2 / 2 instead of the cosine q.g — for a fixed
+// query the same order as ascending |q - g|.  The accumulators of a tile start at -ghn[row] (ghn: [Ng] half squared norms of the gallery
+// rows) instead of 0; the k loop, the masks and the scan are the same.  Cosine (EU = false) never reads ghn.
+template <bool EU>
 __global__ __launch_bounds__(256) void topk_partial_kernel(
     const float* __restrict__ Q, int Nq, const float* __restrict__ G, int Ng, int D, int k, int self_mask,
-    int g_per_slice, int TK_PC, float* __restrict__ pval, int32_t* __restrict__ pidx /* [slices][Nq][k] */) {
+    int g_per_slice, int TK_PC, float* __restrict__ pval, int32_t* __restrict__ pidx /* [slices][Nq][k] */,
+    const float* __restrict__ ghn) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   float* stage = lds;                                   // [2][2][128*32]
   float* lval = lds + 2 * 2 * TK_BQ * TK_BK;             // [4 waves][k][32]
@@ -119,7 +125,12 @@ __global__ __launch_bounds__(256) void topk_partial_kernel(
 #pragma unroll
     for (int ct = 0; ct < 4; ++ct)
 #pragma unroll
-      for (int v = 0; v < 16; ++v) acc[ct][v] = 0.f;
+      for (int v = 0; v < 16; ++v) {
+        if constexpr (EU) {
+          const int gi = g0 + ct * 32 + (v & 3) + 8 * (v >> 2) + 4 * h;
+          acc[ct][v] = gi < gend ? -ghn[gi] : 0.f;
+        } else acc[ct][v] = 0.f;
+      }
     __syncthreads();           // previous tile's readers are done with the staging buffers
     gload(0);
     lwrite(0);
@@ -242,11 +253,12 @@ static __device__ inline unsigned long long tk_now() {
 #define TKC_DECL
 #define TKC_FLUSH do {} while (0)
 #endif
-template <int GS>
+template <int GS, bool EU>
 __global__ __launch_bounds__(256) void topk_partial_dma(
     const float* __restrict__ Q, int Nq, const float* __restrict__ G, int Ng, int D, int k, int self_mask,
     int g_per_slice, int TK_PC, float* __restrict__ pval, int32_t* __restrict__ pidx /* [slices][Nq][k] */,
-    int* __restrict__ gthr /* [Nq] order-preserving int image of a lower bound of query q's final k-th best score */) {
+    int* __restrict__ gthr /* [Nq] order-preserving int image of a lower bound of query q's final k-th best score */,
+    const float* __restrict__ ghn) {
   TKC_DECL
   extern __shared__ __attribute__((aligned(16))) float lds[];
   constexpr int STAGE_FLOATS = (TK_BQ + TK_BG) * TK_BK;
@@ -393,7 +405,12 @@ __global__ __launch_bounds__(256) void topk_partial_dma(
 #pragma unroll
     for (int ct = 0; ct < 4; ++ct)
 #pragma unroll
-      for (int v = 0; v < 16; ++v) acc[ct][v] = 0.f;
+      for (int v = 0; v < 16; ++v) {
+        if constexpr (EU) {              // (D > 512: a tile is >= 17 k-tiles of matrix work, the load's latency is not worth a prefetch)
+          const int gi = gbeg + tile * TK_BG + ct * 32 + (v & 3) + 8 * (v >> 2) + 4 * h;
+          acc[ct][v] = gi < gend ? -ghn[gi] : 0.f;
+        } else acc[ct][v] = 0.f;
+      }
     for (int s0 = 0; s0 < nkp; s0 += 2) {
 #pragma unroll
       for (int sidx = 0; sidx < 2; ++sidx) {
@@ -488,6 +505,27 @@ __global__ __launch_bounds__(256) void topk_partial_dma(
   }
 }
 
+// EU: the accumulators of a tile start at -|g|^2 / 2 of their gallery row.  bn holds the half norms of rows 2 lane and 2 lane + 1 of
+// the tile; they go through the wave's own 128-float LDS slot bw (LDS operations of one wave execute in order: no workgroup barrier)
+// to the lanes that need them — the row of acc[ct][v] in lane (r, h) is ct * 32 + (v & 3) + 8 (v >> 2) + 4 h, four consecutive rows
+// per f32x4.
+__device__ __forceinline__ void tk_bias_init(f32x16 (&acc)[4], float* bw, const float (&bn)[2], int lane, int h) {
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();                              // the previous tile's reads of bw are done
+  bw[2 * lane] = bn[0];
+  bw[2 * lane + 1] = bn[1];
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+#pragma unroll
+  for (int ct = 0; ct < 4; ++ct)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const f32x4 b = *(const f32x4*)&bw[ct * 32 + 8 * j + 4 * h];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) acc[ct][4 * j + i] = -b[i];
+    }
+}
+
 // D <= 512: the QUERY operand lives in registers.  At one workgroup per CU (the lists fill the LDS) a SIMD holds a single wave,
 // so whatever a k-tile does before its first MFMA — wait for the DMA, barrier, issue the next DMA, fetch the first fragments
 // from LDS — leaves the matrix pipe idle (the 2-stage kernel above spends 20 % of its k loop that way).  Here
@@ -498,13 +536,17 @@ __global__ __launch_bounds__(256) void topk_partial_dma(
 //  * the barrier of step s publishes stage s + 1, so the last quarter of step s already fetches the first fragments of step
 //    s + 1: after the next barrier the MFMAs start at once.
 // Same k order inside every accumulator as topk_partial_dma, same scan / drain / bound logic: bit-identical lists.
-template <int NK, int GS>
+//
+// EU: the 128 half norms of a tile are fetched during the PREVIOUS tile (two per lane, at its second k-step: a full k-tile before the
+// counted wait that covers them) and start the accumulators through a per-wave LDS slot — no load latency in front of a tile's first MFMA.
+template <int NK, int GS, bool EU>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void topk_partial_qreg(
     const float* __restrict__ Q, int Nq, const float* __restrict__ G, int Ng, int D, int k, int self_mask,
     int g_per_slice, int TK_PC, float* __restrict__ pval, int32_t* __restrict__ pidx /* [slices][Nq][k] */,
     int* __restrict__ gthr, int gstep /* gallery row r of this launch = row r * gstep of G (a strided SAMPLE; 1 = all rows) */,
     const int* __restrict__ qmap /* query slot q reads row qmap[q] of Q (NULL: q) */,
-    const int* __restrict__ nq_dev /* number of query slots in use, read on the device (NULL: Nq) */) {
+    const int* __restrict__ nq_dev /* number of query slots in use, read on the device (NULL: Nq) */,
+    const float* __restrict__ ghn /* EU: [Ng * gstep] half squared norms, row r of this launch at ghn[r * gstep] */) {
   TKC_DECL
   extern __shared__ __attribute__((aligned(16))) float lds[];
   static_assert(NK % 4 == 0, "a gallery tile is a whole number of ring turns");
@@ -526,6 +568,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   unsigned long long* hp = heaps + wave * kh * 32;
   unsigned long long* pq = pend + wave * TK_PC * 64;
   int* wflag = (int*)(pend + 4 * TK_PC * 64);                  // collective drains, see topk_partial_dma
+  float* bw = (float*)(wflag + 4) + wave * TK_BG;              // EU: this wave's copy of the tile's half norms
   if (tid < 2) wflag[tid] = 0;
   int pc = 0;
   const unsigned long long KEY_EMPTY = tk_key(-INFINITY, INT_MAX), KEY_PAD = ~0ull;
@@ -535,6 +578,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   const bool owner = h == 0 && q < Nq;
   unsigned long long root = KEY_EMPTY;
   float thr = owner ? -INFINITY : INFINITY;
+  float bn[2] = {0.f, 0.f};                                    // EU: half norms of rows 2 lane, 2 lane + 1 of the next tile
 
   // lane (r, h) of MFMA step (kt, qd, t) multiplies by Q[q][32 kt + 8 qd + 4 h + t]
   f32x4 qr[NK][4];
@@ -564,6 +608,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   for (int i = 0; i < 4; ++i) goff[i] = (unsigned)(srow + 32 * i) * rowb + (unsigned)(cq * 16);
   const int klim = D - cq * 4;
   const int ntile = (gend - gbeg + TK_BG - 1) / TK_BG;
+  auto bias_fetch = [&](int tile) {
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const int gi = gbeg + tile * TK_BG + 2 * lane + u;
+      bn[u] = gi < gend ? ghn[(int64_t)gi * gstep] : 0.f;      // rows past the slice are masked to -inf after the k loop
+    }
+  };
   // the DMAs of ring step (tile, kt): k-tiles past D are all-zero, a tile past the end is all out of range
   auto issue = [&](int tile, int kt, int stage) {
     float* Gs = lds + stage * STAGE_FLOATS;
@@ -618,6 +669,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   f32x16 acc[4];
   f32x4 a[2][4];                                               // gallery fragments, double-buffered ACROSS k-tiles
   int gimg = (int)0x807FFFFF;                                  // order-preserving int image of -inf
+  if constexpr (EU) bias_fetch(0);
   issue(0, 0, 0);
   issue(NK > 1 ? 0 : 1, NK > 1 ? 1 : 0, 1);
   issue(NK > 2 ? 0 : 1, NK > 2 ? 2 : 0, 2);
@@ -629,15 +681,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 #ifdef TK_COUNT
     const unsigned long long ts0_ = tk_now();
 #endif
+    if constexpr (EU) tk_bias_init(acc, bw, bn, lane, h);
+    else {
 #pragma unroll
-    for (int ct = 0; ct < 4; ++ct)
+      for (int ct = 0; ct < 4; ++ct)
 #pragma unroll
-      for (int v = 0; v < 16; ++v) acc[ct][v] = 0.f;
+        for (int v = 0; v < 16; ++v) acc[ct][v] = 0.f;
+    }
 #pragma unroll
     for (int kt = 0; kt < NK; ++kt) {
       // step s = (tile, kt) computes from stage kt & 3.  Outstanding here: the DMAs of steps s + 1 and s + 2 (4 each).
       asm volatile("s_waitcnt vmcnt(4)" ::: "memory");         // step s + 1 has landed (this wave's part of it)
       __builtin_amdgcn_s_barrier();                            // ... everybody's; and stage (kt + 3) & 3 has been read by all
+      if constexpr (EU)
+        if (kt == 1) bias_fetch(tile + 1);                     // issued BEFORE step s + 3's DMAs: the wait at step s + 1 covers it
       {
         const int kn = kt + 3;                                  // step s + 3
         issue(kn >= NK ? tile + 1 : tile, kn >= NK ? kn - NK : kn, kn & 3);
@@ -786,10 +843,11 @@ __global__ __launch_bounds__(256) void topk_thresholds(const float* __restrict__
     }
 }
 
-template <int NK, int GS>
+template <int NK, int GS, bool EU>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void topk_collect_qreg(
     const float* __restrict__ Q, int Nq, const float* __restrict__ G, int Ng, int D, int self_mask, int g_per_slice, int TK_PC,
-    const float* __restrict__ tau, int* __restrict__ cnt, unsigned long long* __restrict__ cand /* [Nq][cap] keys */, int cap) {
+    const float* __restrict__ tau, int* __restrict__ cnt, unsigned long long* __restrict__ cand /* [Nq][cap] keys */, int cap,
+    const float* __restrict__ ghn /* EU: [Ng] half squared norms (see topk_partial_qreg) */) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   static_assert(NK % 4 == 0, "a gallery tile is a whole number of ring turns");
   constexpr int STAGE_FLOATS = TK_BG * TK_BK;                  // gallery rows only
@@ -801,6 +859,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   const int gbeg = blockIdx.y * g_per_slice;
   const int gend = min(gbeg + g_per_slice, Ng);
   unsigned long long* pq = pend + wave * TK_PC * 64;
+  float* bw = (float*)(pend + 4 * TK_PC * 64) + wave * TK_BG;  // EU: this wave's copy of the tile's half norms
+  float bn[2] = {0.f, 0.f};
   int pc = 0;
   const int q = q0 + 32 * wave + r;
   // both halves of a lane pair serve query r and test against its threshold; slots past Nq never see a candidate
@@ -827,6 +887,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   for (int i = 0; i < 4; ++i) goff[i] = ((unsigned)(srow + 32 * i) * (unsigned)D + cq * 4) * 4u;
   const int klim = D - cq * 4;
   const int ntile = (gend - gbeg + TK_BG - 1) / TK_BG;
+  auto bias_fetch = [&](int tile) {
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const int gi = gbeg + tile * TK_BG + 2 * lane + u;
+      bn[u] = gi < gend ? ghn[gi] : 0.f;
+    }
+  };
   auto issue = [&](int tile, int kt, int stage) {
     float* Gs = lds + stage * STAGE_FLOATS;
     const bool kin = kt * TK_BK < klim && tile < ntile;
@@ -852,6 +919,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   };
   f32x16 acc[4];
   f32x4 a[2][4];
+  if constexpr (EU) bias_fetch(0);
   issue(0, 0, 0);
   issue(NK > 1 ? 0 : 1, NK > 1 ? 1 : 0, 1);
   issue(NK > 2 ? 0 : 1, NK > 2 ? 2 : 0, 2);
@@ -860,15 +928,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 #pragma unroll
   for (int ct = 0; ct < 4; ++ct) a[0][ct] = *(const f32x4*)&lds[tk_off(32 * ct + r, h)];
   for (int tile = 0; tile < ntile; ++tile) {
+    if constexpr (EU) tk_bias_init(acc, bw, bn, lane, h);
+    else {
 #pragma unroll
-    for (int ct = 0; ct < 4; ++ct)
+      for (int ct = 0; ct < 4; ++ct)
 #pragma unroll
-      for (int v = 0; v < 16; ++v) acc[ct][v] = 0.f;
+        for (int v = 0; v < 16; ++v) acc[ct][v] = 0.f;
+    }
 #pragma unroll
     for (int kt = 0; kt < NK; ++kt) {
       // (a drain's stores and atomic may sit among the outstanding DMAs: they only make this wait stricter)
       asm volatile("s_waitcnt vmcnt(4)" ::: "memory");         // step s + 1 has landed (this wave's part of it)
       __builtin_amdgcn_s_barrier();                            // ... everybody's; and stage (kt + 3) & 3 has been read by all
+      if constexpr (EU)
+        if (kt == 1) bias_fetch(tile + 1);                     // (see topk_partial_qreg)
       {
         const int kn = kt + 3;
         issue(kn >= NK ? tile + 1 : tile, kn >= NK ? kn - NK : kn, kn & 3);
@@ -936,11 +1009,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 // involved; 45 stages for the usual ~400 candidates (padded to 512) — and the first k leave in one coalesced store.  (k rounds of a
 // wave-wide maximum over keys in registers took 135-154 us for 10k queries at k = 50: twelve dependent ds_bpermute round trips per round.)
 // More than TKS_NP keys (rare): k rounds over the keys in memory.  n < k or n > cap: the query goes on the fallback list and its output
-// row is left to that pass.
+// row is left to that pass.  DIST = false (the euclidean search, whose keys hold q.g - |g|^2 / 2): indices only, out_dist is not written.
 #define TKS_NP 1024
 #ifndef TKS_WAVES
 #define TKS_WAVES 1           // queries (waves) per workgroup (4 / 2 / 1 measured 141 / 122 / 119 us for 10k queries: scripts/r5/ab_select.sh)
 #endif
+template <bool DIST>
 __global__ __launch_bounds__(64 * TKS_WAVES) void topk_select(const unsigned long long* __restrict__ cand, const int* __restrict__ cnt, int Nq, int k, int cap,
                                                    int32_t* __restrict__ out_idx, float* __restrict__ out_dist, int* __restrict__ failq,
                                                    int* __restrict__ nfail) {
@@ -975,7 +1049,7 @@ __global__ __launch_bounds__(64 * TKS_WAVES) void topk_select(const unsigned lon
     for (int o = lane; o < k; o += 64) {
       const unsigned long long e = key[o];
       out_idx[(int64_t)q * k + o] = tk_key_index(e);
-      out_dist[(int64_t)q * k + o] = fminf(fmaxf(1.0f - tk_key_score(e), 0.f), 2.f);
+      if constexpr (DIST) out_dist[(int64_t)q * k + o] = fminf(fmaxf(1.0f - tk_key_score(e), 0.f), 2.f);
     }
   } else {
     unsigned long long last = ~0ull;                           // every key still in play is < last
@@ -993,7 +1067,7 @@ __global__ __launch_bounds__(64 * TKS_WAVES) void topk_select(const unsigned lon
       }
       if (lane == 0) {
         out_idx[(int64_t)q * k + o] = tk_key_index(b);
-        out_dist[(int64_t)q * k + o] = fminf(fmaxf(1.0f - tk_key_score(b), 0.f), 2.f);
+        if constexpr (DIST) out_dist[(int64_t)q * k + o] = fminf(fmaxf(1.0f - tk_key_score(b), 0.f), 2.f);
       }
       last = b;
     }
@@ -1002,8 +1076,10 @@ __global__ __launch_bounds__(64 * TKS_WAVES) void topk_select(const unsigned lon
 
 // one WAVE per query: the slices' lists (slices * k entries, unsorted) are spread over the lanes' registers (up to
 // TKM_PER per lane, else the tail is re-read from memory), then k rounds of: lane-local best -> wave arg-best by
-// shuffles -> the owner retires that entry.  Order: larger s first, ties -> lower gallery index.
+// shuffles -> the owner retires that entry.  Order: larger s first, ties -> lower gallery index.  DIST = false: indices only (see
+// topk_select).
 #define TKM_PER 32
+template <bool DIST>
 __global__ __launch_bounds__(256) void topk_merge_kernel(const float* __restrict__ pval, const int32_t* __restrict__ pidx,
                                                          int slices, int Nq, int k, int32_t* __restrict__ out_idx,
                                                          float* __restrict__ out_dist, const int* __restrict__ qmap /* output row of list q (NULL: q) */,
@@ -1041,9 +1117,11 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(const float* __restrict
     }
     if (lane == 0) {
       out_idx[qo * k + o] = wi == INT_MAX ? -1 : wi;
-      float d = 1.0f - ws;
-      d = fminf(fmaxf(d, 0.f), 2.f);
-      out_dist[qo * k + o] = wi == INT_MAX ? INFINITY : d;
+      if constexpr (DIST) {
+        float d = 1.0f - ws;
+        d = fminf(fmaxf(d, 0.f), 2.f);
+        out_dist[qo * k + o] = wi == INT_MAX ? INFINITY : d;
+      }
     }
   }
 }
@@ -1188,23 +1266,27 @@ extern "C" size_t slic_cosine_topk_workspace_bytes(int Nq, int Ng, int k) {
 // The streaming launch (topk_stream) and the collect path's sample pass (topk_collect) launch the SAME topk_partial_qreg instantiations with
 // different dynamic-LDS sizes.  Two per-call-site "largest size set so far" caches could lower the attribute under each other's feet (the
 // smaller call site overwriting the larger one's value: ADVICE round 5); the attribute is therefore set ONCE, for every instantiation, to
-// the device maximum (160 KB) — every launch size of either site fits below it.
+// the device maximum (160 KB) — every launch size of either site fits below it.  Both metrics' instantiations are set together, so a
+// euclidean call and a cosine call cannot lower each other's attribute either.  (The other caches below are statics of the metric's own
+// template instance of topk_stream / topk_collect: each sets its own kernels only.)
 static int topk_qreg_lds_attr() {
   static bool done = false;
   if (done) return SLIC_OK;
   constexpr int LDS_MAX = 160 * 1024;
-  SLIC_HIP_CHECK(hipFuncSetAttribute((const void*)topk_partial_qreg<16, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX));
-  SLIC_HIP_CHECK(hipFuncSetAttribute((const void*)topk_partial_qreg<8, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX));
-  SLIC_HIP_CHECK(hipFuncSetAttribute((const void*)topk_partial_qreg<4, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX));
-  SLIC_HIP_CHECK(hipFuncSetAttribute((const void*)topk_partial_qreg<16, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX));
-  SLIC_HIP_CHECK(hipFuncSetAttribute((const void*)topk_partial_qreg<8, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX));
-  SLIC_HIP_CHECK(hipFuncSetAttribute((const void*)topk_partial_qreg<4, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX));
+#define TK_ATTR_Q(NK, GS, EU) SLIC_HIP_CHECK(hipFuncSetAttribute((const void*)topk_partial_qreg<NK, GS, EU>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX))
+  TK_ATTR_Q(16, 4, false); TK_ATTR_Q(8, 4, false); TK_ATTR_Q(4, 4, false); TK_ATTR_Q(16, 2, false); TK_ATTR_Q(8, 2, false); TK_ATTR_Q(4, 2, false);
+  TK_ATTR_Q(16, 4, true); TK_ATTR_Q(8, 4, true); TK_ATTR_Q(4, 4, true); TK_ATTR_Q(16, 2, true); TK_ATTR_Q(8, 2, true); TK_ATTR_Q(4, 2, true);
+#undef TK_ATTR_Q
   done = true;
   return SLIC_OK;
 }
 
+// EU: per-wave LDS slot of a tile's half norms in the register-operand kernels (tk_bias_init)
+#define TK_EU_LDS(EU) ((EU) ? (size_t)4 * TK_BG * sizeof(float) : (size_t)0)
+
+template <bool EU>
 static int topk_stream(const float* Qn, int Nq, const float* Gn, int Ng, int D, int k, int self_mask, int32_t* out_idx, float* out_dist,
-                       SlicCarver& w, hipStream_t st, const int* qmap, const int* nq_dev) {
+                       const float* ghn, SlicCarver& w, hipStream_t st, const int* qmap, const int* nq_dev) {
   const int slices = topk_slices(Nq, Ng, k);
   int per = (int)slic_cdiv(Ng, slices);
   per = (int)slic_cdiv(per, TK_BG) * TK_BG;
@@ -1213,14 +1295,14 @@ static int topk_stream(const float* Qn, int Nq, const float* Gn, int Ng, int D, 
   int32_t* pidx = w.take<int32_t>((size_t)slices * Nq * k);
   // LDS: 2 ring stages + heaps [4][kh][32] keys (kh = k rounded up to 4 m + 1) + pending [4][pcap][64] keys, one column per LANE
   const int kh = 1 + ((k + 2) / 4) * 4;
-  const size_t fixed = (size_t)2 * 2 * TK_BQ * TK_BK * sizeof(float) + (size_t)4 * kh * 32 * 8;
+  const size_t fixed = (size_t)2 * 2 * TK_BQ * TK_BK * sizeof(float) + (size_t)4 * kh * 32 * 8 + TK_EU_LDS(EU);
   int pcap = (int)((160 * 1024 - 16 - fixed) / (4 * 64 * 8));
   pcap = pcap > TK_PC_MAX ? TK_PC_MAX : pcap;
   SLIC_REQUIRE(pcap >= 2, "slic_cosine_topk: k = %d leaves no LDS for the pending buffers", k);
   const size_t lds = fixed + (size_t)4 * pcap * 64 * 8 + 16;
   static size_t lds_set = 0;
   if (lds > lds_set) {
-    SLIC_HIP_CHECK(hipFuncSetAttribute((const void*)topk_partial_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    SLIC_HIP_CHECK(hipFuncSetAttribute((const void*)topk_partial_kernel<EU>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     lds_set = lds;
   }
   dim3 grid((unsigned)slic_cdiv(Nq, TK_BQ), (unsigned)S);
@@ -1230,8 +1312,8 @@ static int topk_stream(const float* Qn, int Nq, const float* Gn, int Ng, int D, 
   if (dma_ok) {
     static size_t lds_set2 = 0;
     if (lds > lds_set2) {
-      SLIC_HIP_CHECK(hipFuncSetAttribute((const void*)topk_partial_dma<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      SLIC_HIP_CHECK(hipFuncSetAttribute((const void*)topk_partial_dma<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      SLIC_HIP_CHECK(hipFuncSetAttribute((const void*)topk_partial_dma<4, EU>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      SLIC_HIP_CHECK(hipFuncSetAttribute((const void*)topk_partial_dma<2, EU>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
       lds_set2 = lds;
     }
     int* gthr = w.take<int>((size_t)Nq);
@@ -1239,7 +1321,7 @@ static int topk_stream(const float* Qn, int Nq, const float* Gn, int Ng, int D, 
 #ifndef TK_NO_QREG
     if (D <= 512) {
       { const int rc_ = topk_qreg_lds_attr(); if (rc_) return rc_; }
-#define TK_LAUNCH_QREG(NK, GS) topk_partial_qreg<NK, GS><<<grid, dim3(256), lds, st>>>(Qn, Nq, Gn, Ng, D, k, self_mask, per, pcap, pval, pidx, gthr, 1, qmap, nq_dev)
+#define TK_LAUNCH_QREG(NK, GS) topk_partial_qreg<NK, GS, EU><<<grid, dim3(256), lds, st>>>(Qn, Nq, Gn, Ng, D, k, self_mask, per, pcap, pval, pidx, gthr, 1, qmap, nq_dev, ghn)
       if (pcap >= 12) {                                       // pending columns long enough for groups of four scores
         if (D > 256) TK_LAUNCH_QREG(16, 4); else if (D > 128) TK_LAUNCH_QREG(8, 4); else TK_LAUNCH_QREG(4, 4);
       } else {
@@ -1248,20 +1330,21 @@ static int topk_stream(const float* Qn, int Nq, const float* Gn, int Ng, int D, 
 #undef TK_LAUNCH_QREG
     } else
 #endif
-    if (pcap >= 12) topk_partial_dma<4><<<grid, dim3(256), lds, st>>>(Qn, Nq, Gn, Ng, D, k, self_mask, per, pcap, pval, pidx, gthr);
-    else topk_partial_dma<2><<<grid, dim3(256), lds, st>>>(Qn, Nq, Gn, Ng, D, k, self_mask, per, pcap, pval, pidx, gthr);
+    if (pcap >= 12) topk_partial_dma<4, EU><<<grid, dim3(256), lds, st>>>(Qn, Nq, Gn, Ng, D, k, self_mask, per, pcap, pval, pidx, gthr, ghn);
+    else topk_partial_dma<2, EU><<<grid, dim3(256), lds, st>>>(Qn, Nq, Gn, Ng, D, k, self_mask, per, pcap, pval, pidx, gthr, ghn);
   } else
-  topk_partial_kernel<<<grid, dim3(256), lds, st>>>(Qn, Nq, Gn, Ng, D, k, self_mask, per, (2 * pcap) & ~1, pval, pidx);
+  topk_partial_kernel<EU><<<grid, dim3(256), lds, st>>>(Qn, Nq, Gn, Ng, D, k, self_mask, per, (2 * pcap) & ~1, pval, pidx, ghn);
   SLIC_LAUNCH_CHECK();
   SLIC_REQUIRE((int64_t)S * k <= 64 * TKM_PER, "slic_cosine_topk: slices * k = %d exceeds the merge kernel's %d entries", S * k, 64 * TKM_PER);
-  topk_merge_kernel<<<dim3((unsigned)slic_cdiv(Nq, 4)), dim3(256), 0, st>>>(pval, pidx, S, Nq, k, out_idx, out_dist, qmap, nq_dev);
+  topk_merge_kernel<!EU><<<dim3((unsigned)slic_cdiv(Nq, 4)), dim3(256), 0, st>>>(pval, pidx, S, Nq, k, out_idx, out_dist, qmap, nq_dev);
   SLIC_LAUNCH_CHECK();
   return SLIC_OK;
 }
 
 // threshold -> collect -> select -> exact fallback for the queries whose candidate count fell outside [k, cap]
+template <bool EU>
 static int topk_collect(const TopkCollectPlan& c, const float* Qn, int Nq, const float* Gn, int Ng, int D, int k, int self_mask,
-                        int32_t* out_idx, float* out_dist, SlicCarver& w, hipStream_t st) {
+                        int32_t* out_idx, float* out_dist, const float* ghn, SlicCarver& w, hipStream_t st) {
   float* pval1 = w.take<float>((size_t)c.S1 * Nq * c.ms);
   int32_t* pidx1 = w.take<int32_t>((size_t)c.S1 * Nq * c.ms);
   float* tau = w.take<float>((size_t)Nq);
@@ -1273,11 +1356,11 @@ static int topk_collect(const TopkCollectPlan& c, const float* Qn, int Nq, const
   {
     const int kh = 1 + ((c.ms + 2) / 4) * 4;
     const int pcap = TK_PC_MAX;
-    const size_t lds = (size_t)2 * 2 * TK_BQ * TK_BK * sizeof(float) + (size_t)4 * kh * 32 * 8 + (size_t)4 * pcap * 64 * 8 + 16;
+    const size_t lds = (size_t)2 * 2 * TK_BQ * TK_BK * sizeof(float) + (size_t)4 * kh * 32 * 8 + (size_t)4 * pcap * 64 * 8 + 16 + TK_EU_LDS(EU);
     { const int rc_ = topk_qreg_lds_attr(); if (rc_) return rc_; }
     dim3 grid((unsigned)slic_cdiv(Nq, TK_BQ), (unsigned)c.S1);
     const int ns = c.S1 * c.per1;
-#define TK_LAUNCH_S(NK) topk_partial_qreg<NK, 4><<<grid, dim3(256), lds, st>>>(Qn, Nq, Gn, ns, D, c.ms, 0, c.per1, pcap, pval1, pidx1, nullptr, c.gstep, nullptr, nullptr)
+#define TK_LAUNCH_S(NK) topk_partial_qreg<NK, 4, EU><<<grid, dim3(256), lds, st>>>(Qn, Nq, Gn, ns, D, c.ms, 0, c.per1, pcap, pval1, pidx1, nullptr, c.gstep, nullptr, nullptr, ghn)
     if (D > 256) TK_LAUNCH_S(16); else if (D > 128) TK_LAUNCH_S(8); else TK_LAUNCH_S(4);
 #undef TK_LAUNCH_S
     SLIC_LAUNCH_CHECK();
@@ -1291,30 +1374,42 @@ static int topk_collect(const TopkCollectPlan& c, const float* Qn, int Nq, const
     per = (int)slic_cdiv(per, TK_BG) * TK_BG;
     const int S = (int)slic_cdiv(Ng, per);
     const int pcap = TK_PC_MAX;
-    const size_t lds = (size_t)4 * TK_BG * TK_BK * sizeof(float) + (size_t)4 * pcap * 64 * 8;
-    static bool attr_set = false;
+    const size_t lds = (size_t)4 * TK_BG * TK_BK * sizeof(float) + (size_t)4 * pcap * 64 * 8 + TK_EU_LDS(EU);
+    static bool attr_set = false;                              // (one per metric: its own instantiations, its own size)
     if (!attr_set) {
-#define TK_ATTR(NK, GS) SLIC_HIP_CHECK(hipFuncSetAttribute((const void*)topk_collect_qreg<NK, GS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds))
-      TK_ATTR(16, 4); TK_ATTR(8, 4); TK_ATTR(4, 4); TK_ATTR(16, 2); TK_ATTR(8, 2); TK_ATTR(4, 2); TK_ATTR(16, 1); TK_ATTR(8, 1); TK_ATTR(4, 1);
+#define TK_ATTR(NK, GS) SLIC_HIP_CHECK(hipFuncSetAttribute((const void*)topk_collect_qreg<NK, GS, EU>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds))
+      TK_ATTR(16, 4); TK_ATTR(8, 4); TK_ATTR(4, 4);
+      if constexpr (!EU) { TK_ATTR(16, 2); TK_ATTR(8, 2); TK_ATTR(4, 2); TK_ATTR(16, 1); TK_ATTR(8, 1); TK_ATTR(4, 1); }
 #undef TK_ATTR
       attr_set = true;
     }
     dim3 grid((unsigned)slic_cdiv(Nq, TK_BQ), (unsigned)S);
     // scores tested per wave-wide branch: with ~0.4 % of the scores passing, SOME lane of the wave passes in most groups of four, so the
-    // group maximum of the streaming kernels buys little here; SLIC_TOPK_GS = 1 / 2 / 4 selects (experiments; default below)
+    // group maximum of the streaming kernels buys little here; SLIC_TOPK_GS = 1 / 2 / 4 selects (experiments; default below; the euclidean
+    // search keeps the default: its GS = 1 instance at 16 k-tiles would spill)
     const char* ge = getenv("SLIC_TOPK_GS");
     const int gs = ge ? atoi(ge) : 4;
-#define TK_LAUNCH_C(NK, GS) topk_collect_qreg<NK, GS><<<grid, dim3(256), lds, st>>>(Qn, Nq, Gn, Ng, D, self_mask, per, pcap, tau, cnt, cand, c.cap)
-#define TK_LAUNCH_CG(NK) do { if (gs == 1) TK_LAUNCH_C(NK, 1); else if (gs == 2) TK_LAUNCH_C(NK, 2); else TK_LAUNCH_C(NK, 4); } while (0)
+#define TK_LAUNCH_C(NK, GS) topk_collect_qreg<NK, GS, EU><<<grid, dim3(256), lds, st>>>(Qn, Nq, Gn, Ng, D, self_mask, per, pcap, tau, cnt, cand, c.cap, ghn)
+#define TK_LAUNCH_CG(NK) do { if constexpr (EU) TK_LAUNCH_C(NK, 4); else if (gs == 1) TK_LAUNCH_C(NK, 1); else if (gs == 2) TK_LAUNCH_C(NK, 2); else TK_LAUNCH_C(NK, 4); } while (0)
     if (D > 256) TK_LAUNCH_CG(16); else if (D > 128) TK_LAUNCH_CG(8); else TK_LAUNCH_CG(4);
 #undef TK_LAUNCH_CG
 #undef TK_LAUNCH_C
     SLIC_LAUNCH_CHECK();
   }
   // ---- 3. the k best candidates of every query; 4. whoever fell outside [k, TKC_CAP] through the streaming path (normally nobody)
-  topk_select<<<dim3((unsigned)slic_cdiv(Nq, TKS_WAVES)), dim3(64 * TKS_WAVES), 0, st>>>(cand, cnt, Nq, k, c.cap, out_idx, out_dist, failq, nfail);
+  topk_select<!EU><<<dim3((unsigned)slic_cdiv(Nq, TKS_WAVES)), dim3(64 * TKS_WAVES), 0, st>>>(cand, cnt, Nq, k, c.cap, out_idx, out_dist, failq, nfail);
   SLIC_LAUNCH_CHECK();
-  return topk_stream(Qn, Nq, Gn, Ng, D, k, self_mask, out_idx, out_dist, w, st, failq, nfail);
+  return topk_stream<EU>(Qn, Nq, Gn, Ng, D, k, self_mask, out_idx, out_dist, ghn, w, st, failq, nfail);
+}
+
+// the path choice of slic_cosine_topk_plan, for either metric
+template <bool EU>
+static int topk_search(const float* Qn, int Nq, const float* Gn, int Ng, int D, int k, int self_mask, int32_t* out_idx, float* out_dist,
+                       const float* ghn, SlicCarver& w, hipStream_t st) {
+  const TopkCollectPlan c = topk_collect_plan(Nq, Ng, k);
+  if (c.on && D <= 512 && (int64_t)Ng * D * 4 < (1ll << 31))
+    return topk_collect<EU>(c, Qn, Nq, Gn, Ng, D, k, self_mask, out_idx, out_dist, ghn, w, st);
+  return topk_stream<EU>(Qn, Nq, Gn, Ng, D, k, self_mask, out_idx, out_dist, ghn, w, st, nullptr, nullptr);
 }
 
 extern "C" int slic_cosine_topk_plan(int Nq, int Ng, int D, int k, int* out) {
@@ -1332,12 +1427,8 @@ extern "C" int slic_cosine_topk(const float* Qn, int Nq, const float* Gn, int Ng
   SLIC_REQUIRE(Nq > 0 && Ng > 0 && D > 0 && D % 8 == 0 && k >= 1 && k <= TK_KMAX && k <= Ng,
                "slic_cosine_topk: need D %% 8 == 0, 1 <= k <= min(%d, Ng) (Nq=%d Ng=%d D=%d k=%d)", TK_KMAX, Nq, Ng, D, k);
   SLIC_REQUIRE(((uintptr_t)Qn % 16) == 0 && ((uintptr_t)Gn % 16) == 0, "slic_cosine_topk: unaligned");
-  hipStream_t st = S_(stream);
   SlicCarver w(workspace);
-  const TopkCollectPlan c = topk_collect_plan(Nq, Ng, k);
-  if (c.on && D <= 512 && (int64_t)Ng * D * 4 < (1ll << 31))
-    return topk_collect(c, Qn, Nq, Gn, Ng, D, k, self_mask, out_idx, out_dist, w, st);
-  return topk_stream(Qn, Nq, Gn, Ng, D, k, self_mask, out_idx, out_dist, w, st, nullptr, nullptr);
+  return topk_search<false>(Qn, Nq, Gn, Ng, D, k, self_mask, out_idx, out_dist, nullptr, w, S_(stream));
 }
 
 extern "C" int slic_topk_merge_lists(const float* pdist, const int32_t* pidx, int W, int Nq, int k, int32_t* out_idx,
@@ -1353,6 +1444,168 @@ extern "C" int slic_pairwise_euclidean(const float* X, int Nx, const float* Y, i
   SLIC_REQUIRE(X && Y && out && Nx > 0 && Ny > 0 && D > 0, "slic_pairwise_euclidean: bad args");
   const int64_t tot = (int64_t)Nx * Ny;
   pairwise_euclid_kernel<<<dim3((unsigned)slic_cdiv(tot, 256)), dim3(256), 0, S_(stream)>>>(X, Nx, Y, Ny, D, out);
+  SLIC_LAUNCH_CHECK();
+  return SLIC_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// Euclidean top-k (slic_euclidean_topk; LOSS.DIST_METRIC 'euclidean' at evaluate.py:130,367): the cosine path's kernels with the
+// score s = q.g - |g|^2 / 2 (for a fixed query: larger s = nearer), then an exact refine.
+//   1. pre-pass: both sets minus ONE centre (the gallery's column mean, float64, fixed summation order: bit-identical run to run),
+//      zero-padded to D % 8 == 0, and |g_c|^2 / 2 of every centred gallery row.  Distances do not change under a common translation,
+//      while the cancellation in |q|^2 + |g|^2 - 2 q.g shrinks from |x|^2 to |x - centre|^2 for embeddings far from the origin.
+//   2. the search (collect or streaming, topk_search<true>) ranks the kk = min(k + EU_MARGIN, 88, Ng) best rows by score;
+//   3. refine: one wave per query recomputes sqrt(sum (q_i - g_i)^2) of those kk rows from the ORIGINAL rows in float64 and keeps the
+//      k nearest, ascending, ties -> lower index: duplicates come back at exactly 0, near-duplicates in their true order, and a row the
+//      fp32 score put up to EU_MARGIN places too low still makes the list.
+// ------------------------------------------------------------------------------------------
+#define EU_CHUNK 64           // rows per partial column sum of the centre
+#define EU_MARGIN 8           // list entries ranked by score beyond k, re-ranked by the direct distance (SLIC_TOPK_EU_MARGIN: experiments)
+#define EU_GRP 4              // candidates a refine wave measures at once (8, with the column loop unrolled twice: 100 registers, half
+                              // the waves, and a median 222 instead of 128 us over the traced calls at 10k x 100k, D = 128 / 512)
+
+// part[chunk][c] = sum of X[r][c] over the chunk's rows, in float64, rows in order
+__global__ __launch_bounds__(256) void eu_colsum_partial(const float* __restrict__ X, int N, int D, int ld, double* __restrict__ part) {
+  const int c = blockIdx.y * 256 + threadIdx.x;
+  if (c >= D) return;
+  const int r0 = blockIdx.x * EU_CHUNK, r1 = min(r0 + EU_CHUNK, N);
+  double s = 0.0;
+#pragma unroll 8
+  for (int r = r0; r < r1; ++r) s += (double)X[(int64_t)r * ld + c];
+  part[(int64_t)blockIdx.x * D + c] = s;
+}
+
+// one WAVE per column: mean[c] = (sum of the chunks' sums) / N — lane l adds chunks l, l + 64, ... in order, then a fixed butterfly
+__global__ __launch_bounds__(256) void eu_colsum_final(const double* __restrict__ part, int chunks, int N, int D, double* __restrict__ mean) {
+  const int c = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (c >= D) return;
+  double s = 0.0;
+  for (int ch = lane; ch < chunks; ch += 64) s += part[(int64_t)ch * D + c];
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+  if (lane == 0) mean[c] = s / (double)N;
+}
+
+// one WAVE per row: out[row][c] = fp32(X[row][c] - mean[c]) for c < D, 0 up to Dp; hn[row] (if given) = |out[row]|^2 / 2 (float64 sum)
+__global__ __launch_bounds__(256) void eu_center_rows(const float* __restrict__ X, int N, int D, int ld, const double* __restrict__ mean,
+                                                      int Dp, float* __restrict__ out, float* __restrict__ hn) {
+  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= N) return;
+  const int lane = threadIdx.x & 63;
+  const float* x = X + row * ld;
+  double s = 0.0;
+  for (int c = lane; c < Dp; c += 64) {
+    const float v = c < D ? (float)((double)x[c] - mean[c]) : 0.f;
+    out[row * Dp + c] = v;
+    s += (double)v * (double)v;
+  }
+  if (hn) {
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    if (lane == 0) hn[row] = (float)(0.5 * s);
+  }
+}
+
+// one WAVE per query: direct distances of its kk candidates (cidx, -1 = empty slot) from the original rows, EU_GRP candidates at a time
+// (lanes over the columns, one butterfly per candidate); then every entry counts the entries that come before it (distance ascending,
+// ties -> lower index, empty slots last) and the first k go out
+__global__ __launch_bounds__(256) void eu_refine(const float* __restrict__ Q, int ldq, const float* __restrict__ G, int ldg, int Nq, int D,
+                                                 const int32_t* __restrict__ cidx, int kk, int k, int32_t* __restrict__ out_idx,
+                                                 float* __restrict__ out_dist) {
+  __shared__ float sd[4][TK_KMAX];
+  __shared__ int si[4][TK_KMAX];
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int q = blockIdx.x * 4 + w;
+  if (q >= Nq) return;                                         // (whole waves leave: no workgroup barrier below)
+  const float* qr = Q + (int64_t)q * ldq;
+  const int32_t* ci = cidx + (int64_t)q * kk;
+  for (int j0 = 0; j0 < kk; j0 += EU_GRP) {
+    const float* g[EU_GRP];
+    double s[EU_GRP];
+#pragma unroll
+    for (int u = 0; u < EU_GRP; ++u) {
+      const int gi = j0 + u < kk ? ci[j0 + u] : -1;
+      g[u] = gi >= 0 ? G + (int64_t)gi * ldg : nullptr;
+      s[u] = 0.0;
+    }
+    for (int c = lane; c < D; c += 64) {
+      const double qv = (double)qr[c];
+#pragma unroll
+      for (int u = 0; u < EU_GRP; ++u)
+        if (g[u]) {
+          const double d = qv - (double)g[u][c];
+          s[u] = fma(d, d, s[u]);
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < EU_GRP; ++u)
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) s[u] += __shfl_xor(s[u], o);
+    if (lane == 0)
+#pragma unroll
+      for (int u = 0; u < EU_GRP; ++u)
+        if (j0 + u < kk) { sd[w][j0 + u] = g[u] ? (float)sqrt(s[u]) : INFINITY; si[w][j0 + u] = ci[j0 + u]; }
+  }
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  for (int t = lane; t < kk; t += 64) {
+    const float d = sd[w][t];
+    const unsigned i = (unsigned)si[w][t];                     // -1 -> the largest index: empty slots sort last
+    int rank = 0;
+    for (int e = 0; e < kk; ++e) {
+      const float de = sd[w][e];
+      const unsigned ie = (unsigned)si[w][e];
+      rank += (de < d || (de == d && ie < i)) ? 1 : 0;
+    }
+    if (rank < k) {
+      out_idx[(int64_t)q * k + rank] = si[w][t];
+      out_dist[(int64_t)q * k + rank] = d;
+    }
+  }
+}
+
+static int eu_list_len(int Ng, int k) {
+  const char* e = getenv("SLIC_TOPK_EU_MARGIN");
+  const int m = e ? atoi(e) : EU_MARGIN;
+  int kk = k + (m > 0 ? m : 0);
+  if (kk > TK_KMAX) kk = TK_KMAX;
+  return kk < Ng ? kk : Ng;
+}
+
+extern "C" size_t slic_euclidean_topk_workspace_bytes(int Nq, int Ng, int D, int k) {
+  if (Nq <= 0 || Ng <= 0 || D <= 0 || k < 1) return 0;
+  const int Dp = (D + 7) / 8 * 8, kk = eu_list_len(Ng, k);
+  const size_t chunks = (size_t)slic_cdiv(Ng, EU_CHUNK);
+  return slic_align_up((size_t)Nq * Dp * 4, 256) + slic_align_up((size_t)Ng * Dp * 4, 256) + slic_align_up((size_t)Ng * 4, 256) +
+         slic_align_up(chunks * D * 8, 256) + slic_align_up((size_t)D * 8, 256) + slic_align_up((size_t)Nq * kk * 4, 256) +
+         slic_cosine_topk_workspace_bytes(Nq, Ng, kk);
+}
+
+// Q [Nq, D] (row stride ldq), G [Ng, D] (ldg): raw rows.  out_idx / out_dist: [Nq, k], ascending euclidean distance.
+extern "C" int slic_euclidean_topk(const float* Q, int Nq, int ldq, const float* G, int Ng, int ldg, int D, int k, int self_mask,
+                                   int32_t* out_idx, float* out_dist, void* workspace, void* stream) {
+  SLIC_REQUIRE(Q && G && out_idx && out_dist && workspace, "slic_euclidean_topk: null pointer");
+  SLIC_REQUIRE(Nq > 0 && Ng > 0 && D > 0 && ldq >= D && ldg >= D && k >= 1 && k <= TK_KMAX && k <= Ng,
+               "slic_euclidean_topk: need ld >= D, 1 <= k <= min(%d, Ng) (Nq=%d Ng=%d D=%d ldq=%d ldg=%d k=%d)", TK_KMAX, Nq, Ng, D, ldq, ldg, k);
+  hipStream_t st = S_(stream);
+  SlicCarver w(workspace);
+  const int Dp = (D + 7) / 8 * 8, kk = eu_list_len(Ng, k);
+  const int chunks = (int)slic_cdiv(Ng, EU_CHUNK);
+  float* Qc = w.take<float>((size_t)Nq * Dp);
+  float* Gc = w.take<float>((size_t)Ng * Dp);
+  float* hn = w.take<float>((size_t)Ng);
+  double* part = w.take<double>((size_t)chunks * D);
+  double* mean = w.take<double>((size_t)D);
+  int32_t* cidx = w.take<int32_t>((size_t)Nq * kk);
+  eu_colsum_partial<<<dim3((unsigned)chunks, (unsigned)slic_cdiv(D, 256)), dim3(256), 0, st>>>(G, Ng, D, ldg, part);
+  SLIC_LAUNCH_CHECK();
+  eu_colsum_final<<<dim3((unsigned)slic_cdiv(D, 4)), dim3(256), 0, st>>>(part, chunks, Ng, D, mean);
+  SLIC_LAUNCH_CHECK();
+  eu_center_rows<<<dim3((unsigned)slic_cdiv(Nq, 4)), dim3(256), 0, st>>>(Q, Nq, D, ldq, mean, Dp, Qc, nullptr);
+  SLIC_LAUNCH_CHECK();
+  eu_center_rows<<<dim3((unsigned)slic_cdiv(Ng, 4)), dim3(256), 0, st>>>(G, Ng, D, ldg, mean, Dp, Gc, hn);
+  SLIC_LAUNCH_CHECK();
+  const int rc = topk_search<true>(Qc, Nq, Gc, Ng, Dp, kk, self_mask, cidx, nullptr, hn, w, st);
+  if (rc) return rc;
+  eu_refine<<<dim3((unsigned)slic_cdiv(Nq, 4)), dim3(256), 0, st>>>(Q, ldq, G, ldg, Nq, D, cidx, kk, k, out_idx, out_dist);
   SLIC_LAUNCH_CHECK();
   return SLIC_OK;
 }

@@ -11,7 +11,9 @@ iic_retrieve_clips.py that sit on the hot path:
 The reference computes an N_q x N_g sklearn cosine_distances matrix on the host and argsorts every row.
 Here the matrix (when a caller really wants it) comes from the fp32-MFMA gather-GEMM with a
 (1 - s, clamp at 0) epilogue, and the top-k paths never build it: `cosine_topk` fuses the similarity GEMM
-with a per-query streaming top-k (csrc/topk.hip).  Plot/heat-map helpers of evaluate.py are out of scope.
+with a per-query streaming top-k (csrc/topk.hip); `euclidean_topk` runs the same kernels on q.g - |g|^2 / 2 and
+recomputes the winners' distances directly (LOSS.DIST_METRIC 'euclidean').  Plot/heat-map helpers of evaluate.py
+are out of scope.
 """
 import ctypes
 import json
@@ -48,6 +50,16 @@ def cosine_topk_sharded(queries, gallery_shard, k, process_group, row_offset=Non
     """Gallery sharded by rows across the ranks of `process_group` (queries replicated): every rank searches its
     shard, the [Nq, k] lists are all-gathered (RCCL) and merged on every GPU.  Returned indices are GLOBAL gallery
     rows (rank order == row order unless `row_offset` is given)."""
+    return _topk_sharded(cosine_topk, queries, gallery_shard, k, process_group, row_offset)
+
+
+def euclidean_topk_sharded(queries, gallery_shard, k, process_group, row_offset=None):
+    """cosine_topk_sharded for the euclidean metric: every rank's lists hold directly computed distances (each
+    shard may centre on its own mean), so the merge orders them exactly as the unsharded search would."""
+    return _topk_sharded(euclidean_topk, queries, gallery_shard, k, process_group, row_offset)
+
+
+def _topk_sharded(search, queries, gallery_shard, k, process_group, row_offset):
     import torch.distributed as dist
     W = dist.get_world_size(process_group)
     g = _dev(gallery_shard)
@@ -57,7 +69,7 @@ def cosine_topk_sharded(queries, gallery_shard, k, process_group, row_offset=Non
     if row_offset is None:
         row_offset = int(sizes[: dist.get_rank(process_group)].sum().item())
     kk = min(k, g.shape[0])
-    idx, dst = cosine_topk(queries, g, k=kk)
+    idx, dst = search(queries, g, k=kk)
     Nq = idx.shape[0]
     pi = torch.full((Nq, k), -1, dtype=torch.int32, device=g.device)
     pd = torch.full((Nq, k), float("inf"), dtype=torch.float32, device=g.device)
@@ -90,6 +102,32 @@ def cosine_topk(queries, gallery=None, k=20):
     ws = _lib.workspace(lib.slic_cosine_topk_workspace_bytes(Nq, Ng, k), q.device, "topk")
     call("slic_cosine_topk", ptr(qn), Nq, ptr(gn), Ng, Dp, k, int(self_mask), ptr(idx), ptr(dist), ptr(ws), stream())
     return idx, dist
+
+
+def euclidean_topk(queries, gallery=None, k=20):
+    """indices [Nq, k] (int32) and euclidean distances [Nq, k] of the k nearest gallery rows, ascending (ties ->
+    lower index); gallery=None searches the queries themselves with the diagonal excluded, as cosine_topk does."""
+    lib = _lib.load()
+    q = _dev(queries)
+    self_mask = gallery is None
+    g = q if self_mask else _dev(gallery)
+    if g.shape[1] != q.shape[1]:
+        raise ValueError("euclidean_topk: queries have %d columns, the gallery %d" % (q.shape[1], g.shape[1]))
+    Nq, Ng, D = q.shape[0], g.shape[0], q.shape[1]
+    idx = torch.empty(Nq, k, dtype=torch.int32, device=q.device)
+    dist = torch.empty(Nq, k, dtype=torch.float32, device=q.device)
+    ws = _lib.workspace(lib.slic_euclidean_topk_workspace_bytes(Nq, Ng, D, k), q.device, "topk")
+    call("slic_euclidean_topk", ptr(q), Nq, q.stride(0), ptr(g), Ng, g.stride(0), D, k, int(self_mask), ptr(idx), ptr(dist),
+         ptr(ws), stream())
+    return idx, dist
+
+
+def _topk_search(dist_metric):
+    if dist_metric == 'cosine':
+        return cosine_topk
+    if dist_metric == 'euclidean':
+        return euclidean_topk
+    raise ValueError("dist_metric must be 'cosine' or 'euclidean', not %r" % (dist_metric,))
 
 
 def get_distance_matrix(x_embeddings, y_embeddings=None, dist_metric='cosine'):
@@ -157,18 +195,22 @@ def get_topk_acc(distance_matrix, x_labels, y_labels=None, top_ks=[1, 5, 10, 20]
     return _acc_from_indices(topk_indices, x_labels, y_labels, top_ks)
 
 
-def get_topk_acc_from_embeddings(x_embeddings, x_labels, y_embeddings=None, y_labels=None, top_ks=[1, 5, 10, 20]):
-    """the same accuracies without the matrix: fused GEMM + top-k on the device"""
-    idx, _ = cosine_topk(x_embeddings, y_embeddings, k=top_ks[-1])
+def get_topk_acc_from_embeddings(x_embeddings, x_labels, y_embeddings=None, y_labels=None, top_ks=[1, 5, 10, 20],
+                                 dist_metric='cosine'):
+    """the same accuracies without the matrix: fused GEMM + top-k on the device ('cosine' or 'euclidean')"""
+    idx, _ = _topk_search(dist_metric)(x_embeddings, y_embeddings, k=top_ks[-1])
     if y_labels is None:
         y_labels = x_labels
     return _acc_from_indices(idx.cpu().numpy(), x_labels, y_labels, top_ks)
 
 
-def topk_retrieval(args=None, X_train=None, y_train=None, X_test=None, y_test=None, ks=(1, 5, 10, 20, 50)):
+def topk_retrieval(args=None, X_train=None, y_train=None, X_test=None, y_test=None, ks=(1, 5, 10, 20, 50),
+                   dist_metric='cosine'):
     """iic_retrieve_clips.py:275-314.  Either `args.feature_dir` holds {train,test}_{feature,class}.npy
     ([V, 10, D] features averaged over the 10 clips, :280,287) or arrays are passed directly.
-    Returns {k: correct}; writes topk_correct.json next to the features like the reference."""
+    Returns {k: correct}; writes topk_correct.json next to the features like the reference.
+    dist_metric: 'cosine' (the reference's) or 'euclidean'."""
+    search = _topk_search(dist_metric)
     feature_dir = getattr(args, "feature_dir", None) if args is not None else None
     if feature_dir is not None:
         X_train = np.load(os.path.join(feature_dir, 'train_feature.npy'))
@@ -187,7 +229,7 @@ def topk_retrieval(args=None, X_train=None, y_train=None, X_test=None, y_test=No
     X_test = X_test.reshape((-1, X_test.shape[-1]))
     y_train, y_test = y_train.reshape(-1), y_test.reshape(-1)
     ks = list(ks)
-    idx, _ = cosine_topk(X_test, X_train, k=min(max(ks), len(X_train)))
+    idx, _ = search(X_test, X_train, k=min(max(ks), len(X_train)))
     lab = y_train[idx.cpu().numpy()]
     hit = lab == y_test[:, None]
     topk_correct = {k: int(hit[:, :k].any(axis=1).sum()) for k in ks}
