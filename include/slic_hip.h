@@ -565,6 +565,30 @@ int slic_euclidean_topk(const float* Q, int Nq, int ldq, const float* G, int Ng,
 int slic_pairwise_euclidean(const float* X, int Nx, const float* Y, int Ny, int D, float* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * DBSCAN, cosine metric (clustering/cluster_masks.py:55-61 -> sklearn.cluster.DBSCAN(eps, min_samples, metric='cosine')):
+ * labels = DBSCAN(eps, min_samples, metric='cosine').fit(X).labels_ of sklearn 1.7 (sklearn/cluster/_dbscan.py:410-438,
+ * _dbscan_inner.pyx).  Rules:
+ *   1. j is in N(i) iff d(i, j) <= eps, d = clip(1 - (x_i . x_j) * inv_i * inv_j, 0, 2) for j != i: the dot of the raw fp32 rows and
+ *      the inverse norms inv = 1 / ||x|| (0 for a zero row) all in float64; d(i, i) = 0 (sklearn's radius search of X against
+ *      itself zeroes the diagonal), so a zero row is its own neighbour and at distance 1 from every other row.  Every
+ *      pair is decided this way (fp32 similarity GEMM, float64 recheck of the scores within a proven error band of 1 - eps), so the
+ *      relation is symmetric and the same in every pass.  sklearn decides in float32: the two agree except within ~1e-6 of eps.
+ *   2. i is core iff |N(i)| >= min_samples (i itself counts when it is its own neighbour).
+ *   3. clusters = connected components of the core rows under the neighbour relation, numbered 0, 1, ... by their smallest row.
+ *   4. a non-core row with a core neighbour takes the smallest cluster number among its core neighbours; other rows are noise, -1.
+ * X: [N, D] fp32, row stride ldx >= D (elements), 1 <= D <= 512.  Outputs (device): labels int32 [N], is_core uint8 [N] (0 / 1),
+ * counts int32 [N] = |N(i)| (NULL: not returned), *n_clusters int32.  All are integers fixed by the rules: two runs are bit-equal.
+ * SLIC_EINVAL for eps < 0, min_samples < 1, D outside [1, 512], N < 1, or rows beyond int32 indices / a 4 GiB padded copy (no wrap).
+ * The N x N matrix is never written; the workspace is O(N * Dp + N) with Dp = D rounded up to 8. */
+size_t slic_dbscan_cosine_workspace_bytes(int64_t N, int D);       /* 0 for sizes slic_dbscan_cosine rejects */
+int slic_dbscan_cosine(const float* X, int64_t N, int ldx, int D, double eps, int min_samples, int32_t* labels, uint8_t* is_core,
+                       int32_t* counts, int32_t* n_clusters, void* workspace, void* stream);
+/* after a slic_dbscan_cosine call with this workspace (synchronises the stream): out_host[0] = pairs rechecked in float64,
+ * [1] link-pass tiles skipped (all rows in one component already), [2] core rows, [3] border candidates, [4..9] ms of the passes
+ * prep / count / compact / link / number / border when SLIC_DBSCAN_TIMING=1 was set at the call (else -1).  Measurement only. */
+int slic_dbscan_cosine_stats(const void* workspace, double* out_host /* [10] */, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Memory-bank NCE (loss/NCE_loss.py:26-88 NCEAverage, :341-352 NCESoftmaxLoss): gather + dot + /T without
  * materialising the gathered rows, its backward wrt the features, the momentum bank update, and the
  * class-0 softmax cross-entropy.  idx / y are int64 (torch.long) as in the reference.

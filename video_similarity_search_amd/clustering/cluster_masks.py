@@ -3,8 +3,9 @@ Drop-in for the reference's clustering/cluster_masks.py on the k-means path:
     preprocess_features_kmeans(data)                                   <- cluster_masks.py:30-34
     fit_cluster(embeddings, method, k, l2normalize, finch_partition)   <- cluster_masks.py:38-98
 Same names, argument meaning, prints and return type (np.ndarray[N] labels).  method='kmeans'
- and method='finch' (§8f row 1: the method the shipped configs select) run on
-the GPU; the other methods the reference dispatches to sklearn on the host raise.
+(SURVEY.md §8 A5/A6), method='finch' (§8f row 1: the method the shipped configs select) and
+method='DBSCAN' (cosine, clustering/dbscan.py) run on the GPU; 'Agglomerative' and 'OPTICS', which the
+reference dispatches to sklearn on the host, raise.
 """
 import numpy as np
 import torch
@@ -41,9 +42,12 @@ def preprocess_features_kmeans(data, kernels=None):
 
 
 def fit_cluster(embeddings, method='Agglomerative', k=1000, l2normalize=True, finch_partition=0,
-                n_init=10, init='k-means++', process_group=None, random_state=None, kernels=None, exchange=None):
-    """Reference signature + keyword-only extras (n_init / init / process_group / random_state / kernels / exchange) that default
-    to the reference's behaviour: KMeans(n_clusters=k, n_init=10).fit(embeddings).labels_.
+                n_init=10, init='k-means++', process_group=None, random_state=None, kernels=None, exchange=None,
+                *, eps=0.14, min_samples=2):
+    """Reference signature + keyword-only extras (n_init / init / process_group / random_state / kernels / exchange / eps /
+    min_samples) that default to the reference's behaviour: KMeans(n_clusters=k, n_init=10).fit(embeddings).labels_, and for
+    method='DBSCAN' DBSCAN(eps=0.14, min_samples=2, metric='cosine').fit(embeddings).labels_ (noise = -1; l2normalize does not
+    apply, as in the reference; `kernels` is then a DBSCAN provider, see clustering/dbscan.py).
     process_group: `embeddings` is this rank's row shard (rank order == row order), the returned labels are this rank's.
     exchange: the sharded Lloyd iteration's one collective — 'allreduce' (RCCL through torch.distributed; the default), 'allgather', or
     'oneshot' (the library's one-shot all-to-all over peer-mapped memory, csrc/oneshot.hip); None reads SLIC_KMEANS_EXCHANGE."""
@@ -60,12 +64,16 @@ def fit_cluster(embeddings, method='Agglomerative', k=1000, l2normalize=True, fi
         print('Taking partition {} from finch'.format(PARTITION))
         print("Fitted " + str(n_clusters) + " clusters with " + str(method))
         return labels
-    if method not in ('kmeans', 'spherical_kmeans'):
+    if method == 'DBSCAN':
+        # cluster_masks.py:55-61: DBSCAN(eps=0.14, min_samples=2, metric='cosine', n_jobs=-1).fit(embeddings)
+        from .dbscan import DBSCAN
+        km = DBSCAN(eps=eps, min_samples=min_samples, metric='cosine', kernels=kernels).fit(embeddings)
+    elif method not in ('kmeans', 'spherical_kmeans'):
         raise NotImplementedError(
-            f"method={method!r}: 'kmeans', 'spherical_kmeans' and 'finch' are on the MI355X hot path (SURVEY.md §8); the "
-            "reference runs the others on the host through sklearn")
-    x = _to_device(embeddings) if kernels is None else kernels.to_device(embeddings)
-    if method == 'spherical_kmeans':
+            f"method={method!r}: 'kmeans', 'spherical_kmeans', 'finch' and 'DBSCAN' are on the MI355X hot path; average-linkage "
+            "agglomerative clustering and OPTICS are sequential algorithms the reference runs on the host through sklearn")
+    elif method == 'spherical_kmeans':
+        x = _to_device(embeddings) if kernels is None else kernels.to_device(embeddings)
         # cluster_masks.py:73-77: SphericalKMeans(n_clusters=k).fit(embeddings) (spherecluster: normalises the rows itself,
         # n_init=10, k-means++, centres renormalised every iteration).  spherecluster is not vendored: parity unpinned.
         print('clustering with spherical kmeans with k={}'.format(k))
@@ -73,6 +81,7 @@ def fit_cluster(embeddings, method='Agglomerative', k=1000, l2normalize=True, fi
         km = KMeans(n_clusters=k, n_init=n_init, init=init, process_group=process_group, random_state=random_state,
                     spherical=True, kernels=kernels, exchange=exchange).fit(x)
     else:
+        x = _to_device(embeddings) if kernels is None else kernels.to_device(embeddings)
         print("k:", k)
         if l2normalize:
             x = preprocess_features_kmeans(x, kernels)

@@ -219,8 +219,9 @@ def iterative_cluster_step(args, cfg, encoder, eval_train_loader, epoch, cuda=Tr
     """online_train.py:605-662: embeddings of the whole train set -> fit_cluster -> NMI/AMI logs -> vid_clusters.txt in
     the dataset's unshuffled order -> barrier.
 
-    Returns (labels, NMI or None): labels = np.int32 [len(dataset)] in DATASET order (the content of vid_clusters.txt,
-    -1 where the eval loader produced no row, e.g. drop_last), identical on every rank.
+    Returns (labels, NMI or None): labels = np.int32 [len(dataset)] in DATASET order, identical on every rank.  It holds -1
+    both where the eval loader produced no row (e.g. drop_last; 'None' in vid_clusters.txt) and for a DBSCAN noise row ('-1'
+    in vid_clusters.txt, as the reference writes it).  DBSCAN takes the gather-to-rank-0 route, as FINCH does.
 
     NUM_GPUS > 1 with k-means (cfg.ITERCLUSTER.SHARDED, default on): the extraction keeps each rank's [N/W, D] rows on
     its GPU (no per-batch all_gather + D2H, evaluate.py:189-193), fit_cluster runs row-sharded over the process group
@@ -312,11 +313,13 @@ def iterative_cluster_step(args, cfg, encoder, eval_train_loader, epoch, cuda=Tr
         except ImportError:
             pass
         # one label per line, unshuffled dataset order (online_train.py:654-657); a slot the loader never produced is
-        # written as the reference writes it ('None')
+        # written as the reference writes it ('None'), a DBSCAN noise row as its label, -1
+        produced = np.zeros(n_data, dtype=bool)
+        produced[np.asarray(idxs, dtype=np.int64).reshape(-1)] = True
         cluster_output_path = os.path.join(cfg.OUTPUT_PATH, 'vid_clusters.txt')
         with open(cluster_output_path, "w") as f:
-            for label in order:
-                f.write('{}\n'.format(label if label >= 0 else None))
+            for label, seen in zip(order, produced):
+                f.write('{}\n'.format(label if seen else None))
         print('Saved cluster labels to', cluster_output_path)
     if cfg.NUM_GPUS > 1 and not sharded:
         # besides the text file (kept for the reference's dataset code, which re-parses it on every
