@@ -565,6 +565,24 @@ int slic_euclidean_topk(const float* Q, int Nq, int ldq, const float* G, int Ng,
 int slic_pairwise_euclidean(const float* X, int Nx, const float* Y, int Ny, int D, float* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The validation pass (validation.py:12-151): the per-batch arithmetic after the encoder.
+ * ------------------------------------------------------------------------------------------ */
+/* validation.py:59-71 as ONE launch on the three [B, D] embedding matrices of a batch: dist_a[b] = d(ex[b], ey[b]) and
+ * dist_b[b] = d(ex[b], ez[b]) with the arithmetic — and the bits — of slic_pair_distance (either may be NULL);
+ * rec[0] = mean_b max(0, dist_a[b] - dist_b[b] + margin)   (MarginRankingLoss(margin)(dist_a, dist_b, -1), mean reduction),
+ * rec[1] = #{b : dist_b[b] - dist_a[b] > 0} / B            (accuracy, models/model_utils.py:232-235), rec[2] = B: one row of the
+ * epoch record.  One workgroup walks the rows; the sums have a fixed order, so the result does not depend on scheduling.
+ * SLIC_EINVAL for B < 1 or D < 1. */
+int slic_triplet_val_batch(const float* ex, const float* ey, const float* ez, int B, int D, int euclid, float margin, float* dist_a,
+                           float* dist_b, float* rec, void* stream);
+/* get_topk_acc's double loop (evaluate.py:296-305) on a device-resident [Nq, k] index table (slic_cosine_topk / slic_euclidean_topk /
+ * slic_topk_merge_lists): first_hit[q] (NULL = not wanted) = the first column j with g_labels[idx[q, j]] == q_labels[q], k if none;
+ * hits[i] = #{q : first_hit[q] < top_ks[i]} — written, not accumulated.  Entries < 0 (merge padding) or >= Ng never hit.  top_ks is
+ * a HOST array of n_ks <= 8 ascending values in 1 .. k; everything else lives on the device.  Integer counts: exact. */
+int slic_topk_label_hits(const int32_t* idx, int Nq, int k, const int64_t* q_labels, const int64_t* g_labels, int Ng,
+                         const int32_t* top_ks, int n_ks, int32_t* first_hit, int32_t* hits, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * DBSCAN, cosine metric (clustering/cluster_masks.py:55-61 -> sklearn.cluster.DBSCAN(eps, min_samples, metric='cosine')):
  * labels = DBSCAN(eps, min_samples, metric='cosine').fit(X).labels_ of sklearn 1.7 (sklearn/cluster/_dbscan.py:410-438,
  * _dbscan_inner.pyx).  Rules:

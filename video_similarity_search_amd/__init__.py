@@ -9,6 +9,8 @@ path behind the reference's Python call surface (rvl-lab-utoronto/video_similari
     clustering.cluster_masks.fit_cluster    <- clustering/cluster_masks.py:38-98 ('kmeans')
     evaluate.get_distance_matrix/get_topk_acc, retrieval.topk_retrieval
                                             <- evaluate.py:208-307, iic_retrieve_clips.py:275-314
+    evaluate.k_nearest_embeddings           <- evaluate.py:353-400 (plot=False)
+    validation.validate                     <- validation.py:12-151
     misc.distributed_helper                 <- misc/distributed_helper.py
 
 All arithmetic runs in hand-written HIP kernels in csrc/ behind the C ABI of include/slic_hip.h

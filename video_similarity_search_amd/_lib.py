@@ -135,6 +135,9 @@ SIGNATURES = {
     "slic_pairwise_euclidean": (I, [P, I, P, I, I, P, P]),
     "slic_euclidean_topk_workspace_bytes": (c_size_t, [I, I, I, I]),
     "slic_euclidean_topk": (I, [P, I, I, P, I, I, I, I, I, P, P, P, P]),
+    # validation pass
+    "slic_triplet_val_batch": (I, [P, P, P, I, I, I, F, P, P, P, P]),
+    "slic_topk_label_hits": (I, [P, I, I, P, P, I, P, I, P, P, P]),
     # DBSCAN (cosine)
     "slic_dbscan_cosine_workspace_bytes": (c_size_t, [L, I]),
     "slic_dbscan_cosine": (I, [P, L, I, I, Dbl, I, P, P, P, P, P, P]),

@@ -10,6 +10,7 @@
 // MFMA roles are swapped (A = column block j, B = row block i) so a lane owns ONE row i and sees 16 j's
 // per accumulator: the softmax reduction stays in registers, then one shuffle + one LDS step.
 #include "common.h"
+#include "pairdist.h"
 #include <math.h>
 
 __global__ void ntxent_normalize(const float* __restrict__ E, int n, int D, int lde,
@@ -130,7 +131,7 @@ __global__ __launch_bounds__(256) void ntxent_bwd_kernel(const float* __restrict
 }
 
 // one wave per row: 1 - cos(x, y) with F.cosine_similarity's per-norm clamp, or ||x - y + 1e-6||_2
-// (F.pairwise_distance default eps) — models/triplet_net.py:29-33
+// (F.pairwise_distance default eps) — models/triplet_net.py:29-33; the arithmetic lives in pairdist.h
 __global__ void pair_distance_kernel(const float* __restrict__ X, const float* __restrict__ Y, int n, int D,
                                      int euclid, float* __restrict__ out) {
   const int row = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
@@ -139,12 +140,9 @@ __global__ void pair_distance_kernel(const float* __restrict__ X, const float* _
   const float* x = X + (int64_t)row * D;
   const float* y = Y + (int64_t)row * D;
   float a = 0.f, b = 0.f, c = 0.f;
-  for (int k = lane; k < D; k += 64) {
-    if (euclid) { const float d = x[k] - y[k] + 1e-6f; a = fmaf(d, d, a); }
-    else { a = fmaf(x[k], y[k], a); b = fmaf(x[k], x[k], b); c = fmaf(y[k], y[k], c); }
-  }
-  for (int o = 32; o > 0; o >>= 1) { a += __shfl_xor(a, o); b += __shfl_xor(b, o); c += __shfl_xor(c, o); }
-  if (lane == 0) out[row] = euclid ? sqrtf(a) : 1.0f - a / (fmaxf(sqrtf(b), 1e-8f) * fmaxf(sqrtf(c), 1e-8f));
+  for (int k = lane; k < D; k += 64) slic_pd_step(x[k], y[k], euclid, a, b, c);
+  slic_pd_wave_sum(a, b, c);
+  if (lane == 0) out[row] = slic_pd_finish(a, b, c, euclid);
 }
 
 // backward of pair_distance_kernel: dX, dY from g = dL/d dist (one wave per row).

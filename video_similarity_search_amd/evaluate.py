@@ -5,6 +5,8 @@ iic_retrieve_clips.py that sit on the hot path:
     get_distance_matrix(x, y=None, dist_metric)           <- evaluate.py:208-223
     get_closest_data_mat(distance_matrix, top_k)          <- evaluate.py:226-231
     get_topk_acc(distance_matrix, x_labels, y_labels, top_ks)   <- evaluate.py:287-307
+    topk_acc_device(x, x_labels, y, y_labels, top_ks, dist_metric)   (the same value, search and counting on the device)
+    k_nearest_embeddings(args, model, ..., plot=False)    <- evaluate.py:353-400
     evaluate(model, data_loader, ...) / get_embeddings_and_labels(...)   <- evaluate.py:146-205, 310-350
     topk_retrieval(args | arrays)                          <- iic_retrieve_clips.py:275-314
 
@@ -202,6 +204,72 @@ def get_topk_acc_from_embeddings(x_embeddings, x_labels, y_embeddings=None, y_la
     if y_labels is None:
         y_labels = x_labels
     return _acc_from_indices(idx.cpu().numpy(), x_labels, y_labels, top_ks)
+
+
+def _labels_dev(labels, device):
+    if torch.is_tensor(labels):
+        return labels.detach().to(device=device, dtype=torch.int64).reshape(-1).contiguous()
+    return torch.as_tensor(np.asarray(labels, dtype=np.int64).reshape(-1)).to(device)
+
+
+def _label_hits(idx, q_labels, g_labels, top_ks, first_hit=None):
+    """slic_topk_label_hits on a device-resident [Nq, k] index table: int32 [len(top_ks)] on the device, hits[i] = the number of
+    query rows with a same-label gallery row among their first top_ks[i] neighbours (the counting of evaluate.py:296-305)"""
+    _lib.require_device(idx)
+    idx = idx.to(torch.int32).contiguous()
+    q, g = _labels_dev(q_labels, idx.device), _labels_dev(g_labels, idx.device)
+    if q.shape[0] != idx.shape[0]:
+        raise ValueError("label_hits: %d query labels for %d rows of indices" % (q.shape[0], idx.shape[0]))
+    ks = (ctypes.c_int32 * len(top_ks))(*[int(k) for k in top_ks])
+    hits = torch.empty(len(top_ks), dtype=torch.int32, device=idx.device)
+    call("slic_topk_label_hits", ptr(idx), idx.shape[0], idx.shape[1], ptr(q), ptr(g), g.shape[0], ks, len(top_ks), ptr(first_hit),
+         ptr(hits), stream())
+    return hits
+
+
+def topk_acc_device(x_embeddings, x_labels, y_embeddings=None, y_labels=None, top_ks=[1, 5, 10, 20], dist_metric='cosine', *,
+                    kernels=None):
+    """the value get_topk_acc returns (np.ndarray[len(top_ks)], float64) with the search AND the counting on the device: top-k
+    search + slic_topk_label_hits, one small read-back of len(top_ks) integers.  Labels: lists, arrays or tensors.
+    kernels: a provider with topk / label_hits (validation.HipValidationKernels' interface) instead of the device."""
+    if kernels is None:
+        idx, _ = _topk_search(dist_metric)(x_embeddings, y_embeddings, k=top_ks[-1])
+        hits = _label_hits(idx, x_labels, x_labels if y_labels is None else y_labels, top_ks)
+    else:
+        idx = kernels.topk(x_embeddings, y_embeddings, top_ks[-1], dist_metric)
+        hits = kernels.label_hits(idx, x_labels, x_labels if y_labels is None else y_labels, top_ks)
+    return hits.cpu().numpy().astype(np.float64) / idx.shape[0]
+
+
+def k_nearest_embeddings(args, model, cuda, device, train_loader, test_loader, train_data, val_data, cfg, test_split='val',
+                         plot=True, epoch=None, is_master_proc=True, evaluate_output=None, num_exemplar=None, service=None,
+                         load_pkl=False, out_filename='global_retrieval_acc', *, kernels=None):
+    """evaluate.py:353-400 with plot=False (what the training loop passes, online_train.py:737-739): embeddings of the test split and
+    of the train split, top-1/5/10/20 retrieval accuracy of test against train on the master, the reference's prints and its line in
+    tnet_checkpoints/<out_filename>.txt.  Returns the four accuracies on the master, [] elsewhere.  train_data / val_data are only
+    used by the plot."""
+    if plot:
+        raise NotImplementedError("k_nearest_embeddings(plot=True): the exemplar plot helpers are out of scope; the training loop "
+                                  "calls it with plot=False (online_train.py:737-739)")
+    if is_master_proc:
+        print('Getting embeddings...')
+    test_embeddings, test_labels, _ = get_embeddings_and_labels(args, cfg, model, cuda, device, test_loader, split=test_split,
+                                                                is_master_proc=is_master_proc, load_pkl=load_pkl)
+    train_embeddings, train_labels, _ = get_embeddings_and_labels(args, cfg, model, cuda, device, train_loader, split='train',
+                                                                  is_master_proc=is_master_proc, load_pkl=load_pkl)
+    acc = []
+    print('Computing top1/5/10/20 Acc...')
+    if (is_master_proc):
+        acc = topk_acc_device(test_embeddings, test_labels, train_embeddings, train_labels, dist_metric=cfg.LOSS.DIST_METRIC,
+                              kernels=kernels)
+        if epoch is not None:
+            # the reference's format string has two placeholders for its four arguments: the file holds top-1 and top-5
+            to_write = 'epoch:{} {:.2f} {:.2f}'.format(epoch, 100.*acc[0], 100.*acc[1], 100.*acc[2], 100.*acc[3])
+            to_write += '\n'
+            from .online_train import _append_log
+            _append_log(cfg, '{}.txt'.format(out_filename), to_write)
+        print('Top1 Acc: {:.2f}%, Top5 Acc: {:.2f}%, Top10 Acc: {:.2f}%, Top20 Acc: {:.2f}%'.format(100.*acc[0], 100.*acc[1], 100.*acc[2], 100.*acc[3]))
+    return acc
 
 
 def topk_retrieval(args=None, X_train=None, y_train=None, X_test=None, y_test=None, ks=(1, 5, 10, 20, 50),
