@@ -607,6 +607,47 @@ int slic_dbscan_cosine(const float* X, int64_t N, int ldx, int D, double eps, in
 int slic_dbscan_cosine_stats(const void* workspace, double* out_host /* [10] */, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Cluster-quality metrics of the cluster step (online_train.py:633-639 -> sklearn.metrics.normalized_mutual_info_score and
+ * adjusted_mutual_info_score, both with average_method='arithmetic'): one call, one fp64 record.  The rules are sklearn 1.7.2's
+ * (sklearn/metrics/cluster/_supervised.py:819-924, :1022-1062, :1146-1174, :1281-1314, _expected_mutual_info_fast.pyx):
+ *   1. classes / clusters = the distinct values of labels_true / labels_pred (np.unique: any int32 value, -1 like any other, gaps
+ *      allowed), numbered in ascending order of value; R = n_classes, C = n_clusters.  n[i][j] = the contingency table, a[i] and
+ *      b[j] its row and column sums (integers: exact in any order).
+ *   2. MI = max(0, sum over the cells n > 0 of t), t = (n/N) * (log n - log N) + (n/N) * (-log(a*b) + log N + log N), a term with
+ *      |t| < 2^-52 counted as 0; MI = 0 when R == 1 or C == 1.
+ *   3. H(x) = -sum_i (x_i / N) * (log x_i - log N); 0 for a single class.
+ *   4. EMI = sum over i, j and n = max(1, a_i + b_j - N) .. min(a_i, b_j) of (n/N) * (log N + log n - log a_i - log b_j) * exp(g), g = the
+ *      log of the hypergeometric weight, sklearn's L(a) + L(b) + L(N-a) + L(N-b) - L(n) - L(N) - L(a-n) - L(b-n) - L(N-a-b+n) with
+ *      L(x) = lgamma(x + 1).  Taken literally its terms are ~N log N (2.7e6 at N = 240 000, one ulp = 4.7e-10) and cancel to ~10, so
+ *      the last bit of lgamma moves EMI by 1e-10.  The same g in exact arithmetic, with L(N) - L(N - x) = x log N + T(x),
+ *      T(x) = sum_{k < x} log1p(-k / N), has no term beyond ~(a + b) log N:
+ *          g = ((((L(a) + L(b)) - L(n)) - L(a-n)) - L(b-n)) - n * log N) + ((T(a+b-n) - T(a)) - T(b))      added in this order,
+ *      L and T from tables of N + 1 doubles built once per call (T by a fixed-order scan); EMI = 0 when R == 1 or C == 1.
+ *   5. NMI = 1 when R == C == 1; else 0 when MI == 0; else MI / ((H_true + H_pred) / 2).
+ *   6. AMI = 1 when R == C == 1; else 0 when R == 1 or C == 1; else num / den with num = MI - EMI, den = (H_true + H_pred) / 2 - EMI,
+ *      each pushed away from 0 to at least 2^-52 in magnitude, keeping its sign (>= 0 counts as positive).
+ * Every fp64 sum has a fixed order: cell (or class) p belongs to thread p mod (1024 * 256) of a 1024 x 256 grid, a thread adds its
+ * terms in ascending p (the n of one cell in ascending n first), a workgroup folds its 256 values by halving (v[t] += v[t + s], s = 128
+ * .. 1), and one workgroup folds the 1024 partial sums (thread t adds partials t, t + 256, t + 512, t + 768, then the same halving).
+ * Two runs on the same labels give the same bits.
+ * labels_true, labels_pred: int32 [N] on the device, unit stride.  record (device, SLIC_METRICS_RECORD doubles): MI, H_true, H_pred, EMI,
+ * NMI, AMI, n_classes, n_clusters, status.  status 0: the record is valid; 1: R * C exceeds max_cells, nothing else was computed
+ * (the other slots hold 0 except the two counts) and the table was not touched.
+ * Limits: 1 <= N <= SLIC_METRICS_MAX_N; the dense R x C int32 table lives in the workspace, which the caller sizes with max_cells,
+ * 1 <= max_cells <= SLIC_METRICS_MAX_CELLS (2^26 cells, 256 MiB: admits 400 x 65536 and 1024 x 65536).  SLIC_EINVAL beyond.  The
+ * workspace is about 61 N + 4 max_cells bytes, sized by the caller's bound and not by the data (the class counts are found on the
+ * device); the table is cleared and read over R * C cells only.
+ * Cost beyond the sizes the cluster step has (N <= 240 000, measured): each of the 16 radix passes ends in a scan of N / 4 ints by ONE
+ * workgroup, and an EMI cell is walked by one thread, so both grow serially: at N = 2^24 a scan covers 4M elements on one compute
+ * unit, and two classes of N / 2 labels make one thread walk N / 2 terms.  Correct at every admitted size; tuned for N ~ 10^5. */
+#define SLIC_METRICS_MAX_N ((int64_t)1 << 24)
+#define SLIC_METRICS_MAX_CELLS ((int64_t)1 << 26)
+#define SLIC_METRICS_RECORD 9
+size_t slic_cluster_metrics_workspace_bytes(int64_t N, int64_t max_cells);       /* 0 for sizes slic_cluster_metrics rejects */
+int slic_cluster_metrics(const int32_t* labels_true, const int32_t* labels_pred, int64_t N, int64_t max_cells, double* record,
+                         void* workspace, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Memory-bank NCE (loss/NCE_loss.py:26-88 NCEAverage, :341-352 NCESoftmaxLoss): gather + dot + /T without
  * materialising the gathered rows, its backward wrt the features, the momentum bank update, and the
  * class-0 softmax cross-entropy.  idx / y are int64 (torch.long) as in the reference.

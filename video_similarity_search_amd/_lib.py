@@ -142,6 +142,9 @@ SIGNATURES = {
     "slic_dbscan_cosine_workspace_bytes": (c_size_t, [L, I]),
     "slic_dbscan_cosine": (I, [P, L, I, I, Dbl, I, P, P, P, P, P, P]),
     "slic_dbscan_cosine_stats": (I, [P, P, P]),
+    # cluster-quality metrics (NMI / AMI)
+    "slic_cluster_metrics_workspace_bytes": (c_size_t, [L, L]),
+    "slic_cluster_metrics": (I, [P, P, L, L, P, P, P]),
     # memory-bank NCE
     "slic_nce_scores_fwd": (I, [P, P, P, I, I, I, F, P, P, P]),
     "slic_nce_scores_bwd": (I, [P, P, P, I, I, I, F, P, P]),

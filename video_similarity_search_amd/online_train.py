@@ -215,7 +215,7 @@ def _cluster_sharded(cfg):
 
 
 def iterative_cluster_step(args, cfg, encoder, eval_train_loader, epoch, cuda=True, device=None, is_master_proc=True,
-                           kmeans_kernels=None):
+                           kmeans_kernels=None, metrics_kernels=None):
     """online_train.py:605-662: embeddings of the whole train set -> fit_cluster -> NMI/AMI logs -> vid_clusters.txt in
     the dataset's unshuffled order -> barrier.
 
@@ -229,7 +229,10 @@ def iterative_cluster_step(args, cfg, encoder, eval_train_loader, epoch, cuda=Tr
     (label, dataset index, true label).  FINCH — and SHARDED = False — keep the reference's shape: gather to every rank,
     cluster on rank 0, and the dataset-ordered labels are broadcast (which is also the barrier of :662).
     `kmeans_kernels`: another kernel provider for fit_cluster (the tests of the multi-process control flow pass a CPU one
-    as an argument; the product passes nothing and runs the HIP kernels)."""
+    as an argument; the product passes nothing and runs the HIP kernels).
+    NMI / AMI come from the device (clustering/metrics.py: one call, one record) when `cuda` is true and a device is present, or
+    when `metrics_kernels` names a provider; a failure there raises.  With cuda=False and no provider the reference's
+    scikit-learn lines run on the host, and are skipped without scikit-learn as before."""
     import numpy as np
     from .clustering.cluster_masks import fit_cluster
     from .evaluate import get_embeddings_and_labels
@@ -300,18 +303,30 @@ def iterative_cluster_step(args, cfg, encoder, eval_train_loader, epoch, cuda=Tr
                 raise
             err = e
     if is_master_proc and order is not None:
-        try:                                     # O(N) contingency-table metrics stay on the host
-            from sklearn.metrics import adjusted_mutual_info_score, normalized_mutual_info_score
-            NMI = normalized_mutual_info_score(true_labels, cluster_labels)
-            AMI = adjusted_mutual_info_score(true_labels, cluster_labels)
+        if metrics_kernels is not None or (cuda and torch.cuda.is_available()):
+            # one device call, one small read-back (clustering/metrics.py); nothing here depends on an optional import
+            from .clustering.metrics import cluster_scores
+            scores = cluster_scores(true_labels, cluster_labels, kernels=metrics_kernels)
+            NMI, AMI = scores['NMI'], scores['AMI']
             print('NMI between true labels and cluster assignments: {:.3f}'.format(NMI))
             print('AMI between true labels and cluster assignments: {:.3f}\n'.format(AMI))
             _append_log(cfg, 'NMIs.txt', 'epoch:{} {:.3f}\n'.format(epoch, NMI))
             _append_log(cfg, 'AMIs.txt', 'epoch:{} {:.3f}\n'.format(epoch, AMI))
             if getattr(cfg.ITERCLUSTER, "ADAPTIVEP", False):
                 cfg.DATASET.POSITIVE_SAMPLING_P = float(1.0 - NMI)
-        except ImportError:
-            pass
+        else:                                    # cuda=False and no provider: the reference's host lines
+            try:
+                from sklearn.metrics import adjusted_mutual_info_score, normalized_mutual_info_score
+                NMI = normalized_mutual_info_score(true_labels, cluster_labels)
+                AMI = adjusted_mutual_info_score(true_labels, cluster_labels)
+                print('NMI between true labels and cluster assignments: {:.3f}'.format(NMI))
+                print('AMI between true labels and cluster assignments: {:.3f}\n'.format(AMI))
+                _append_log(cfg, 'NMIs.txt', 'epoch:{} {:.3f}\n'.format(epoch, NMI))
+                _append_log(cfg, 'AMIs.txt', 'epoch:{} {:.3f}\n'.format(epoch, AMI))
+                if getattr(cfg.ITERCLUSTER, "ADAPTIVEP", False):
+                    cfg.DATASET.POSITIVE_SAMPLING_P = float(1.0 - NMI)
+            except ImportError:
+                pass
         # one label per line, unshuffled dataset order (online_train.py:654-657); a slot the loader never produced is
         # written as the reference writes it ('None'), a DBSCAN noise row as its label, -1
         produced = np.zeros(n_data, dtype=bool)
