@@ -2,6 +2,7 @@
 here, the collect and streaming paths against each other, exactness at duplicates / near-duplicates / far-from-origin data, the
 drop-in accuracies, the sharded merge, and the cosine path left untouched by euclidean calls in the same process."""
 import contextlib
+import ctypes
 import os
 
 import numpy as np
@@ -253,6 +254,58 @@ def test_cosine_unchanged_by_euclidean_calls(gpu):
     after = cos_all()
     for (ia, da), (ib, db) in zip(before, after):
         assert np.array_equal(ia, ib) and np.array_equal(da, db)
+
+
+# One process per line of calls (D = 256: the register-operand kernels with 8 k-tiles; LDS bytes from topk_stream / topk_collect):
+#   "big"     k = 88 on 5000 rows: streaming, 2 or 3 pending slots per lane -> topk_partial_qreg<8, 2, EU> at 162832 B, the largest size
+#   "big4"    k = 40 on 5000 rows: streaming, 27 (euclidean, 48 ranked: 22) pending slots -> topk_partial_qreg<8, 4, EU> at 162832 B
+#   "collect" k = 20 on 40000 rows: the collect path launches the SAME topk_partial_qreg<8, 4, EU> twice with smaller sizes — the
+#             sample pass (<= 16 entries per list: <= 147 KB) and the exact fallback (k = 20, 32 pending slots: 152592 B, +2048 euclidean)
+# so "big4, collect, big4" asks one kernel for 162832, < 150000, 152592 and 162832 bytes again: a limit that followed the last request
+# down would refuse the last launch.
+_LDS_SEQUENCE_CHILD = """
+import sys, numpy as np
+from video_similarity_search_amd.evaluate import cosine_topk, euclidean_topk
+search = {"cosine": cosine_topk, "euclidean": euclidean_topk}[sys.argv[1]]
+rng = np.random.default_rng(91)
+Q = rng.standard_normal((300, 256)).astype(np.float32)
+G = rng.standard_normal((40000, 256)).astype(np.float32)
+calls = {"big": lambda: search(Q, G[:5000], k=88), "big4": lambda: search(Q, G[:5000], k=40), "collect": lambda: search(Q, G, k=20)}
+out = {}
+for n, call in enumerate(sys.argv[3].split(",")):
+    idx, dist = calls[call]()
+    out["idx%d" % n], out["dist%d" % n] = idx.cpu().numpy(), dist.cpu().numpy()
+np.savez(sys.argv[2], **out)
+"""
+
+
+@pytest.mark.parametrize("metric", ["cosine", "euclidean"])
+def test_topk_lds_limit_survives_smaller_launches(gpu, tmp_path, metric):
+    """k = 88 and k = 40 (the largest LDS size of both streaming instantiations), then a collect-path search whose launches ask the
+    k = 40 kernel for less, then k = 40 and k = 88 again, all in ONE process: the smaller requests in between must not lower a
+    limit.  Every result equals the same call's result as the first call of a process."""
+    import subprocess
+    import sys
+    from conftest import ROOT
+    from video_similarity_search_amd import _lib
+    plan = (ctypes.c_int * 6)()
+    for k, on in ((20, 1), (28, 1), (40, 0), (48, 0), (88, 0)):          # (28 / 48: what the euclidean search ranks for k = 20 / 40)
+        _lib.check(gpu.slic_cosine_topk_plan(300, 40000 if on else 5000, 256, k, plan), "slic_cosine_topk_plan")
+        assert plan[0] == on, (k, "the middle search must take the collect path, the others the streaming path")
+
+    def child(calls):
+        f = str(tmp_path / (calls.replace(",", "_") + ".npz"))
+        env = dict(os.environ, PYTHONPATH=ROOT)
+        env.pop("SLIC_TOPK_COLLECT", None)
+        r = subprocess.run([sys.executable, "-c", _LDS_SEQUENCE_CHILD, metric, f, calls], env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-2000:])
+        return dict(np.load(f))
+    order = ("big", "big4", "collect", "big4", "big")
+    seq = child(",".join(order))
+    fresh = {c: child(c) for c in set(order)}
+    for n, c in enumerate(order):
+        assert np.array_equal(seq["idx%d" % n], fresh[c]["idx0"]) and np.array_equal(seq["dist%d" % n], fresh[c]["dist0"]), (metric, n, c)
+    assert [seq["idx%d" % n].shape[1] for n in range(5)] == [88, 40, 20, 40, 88]
 
 
 def test_euclidean_topk_errors(gpu):

@@ -384,7 +384,6 @@ __global__ void colsum_kernel(const float* __restrict__ x, int64_t M, int C, flo
                           // (0.65-0.8 ms of a 36.7 ms step; level + final as ONE launch with a last-workgroup ticket measured equal to the two launches,
                           // 36.70 vs 36.71 ms, for the second time — round 2 — and is not kept)
 #endif
-static inline hipStream_t S_(void* s) { return (hipStream_t)s; }
 static inline unsigned ew_grid(int64_t tot) {
   int64_t g = slic_cdiv(tot, 256);
   return (unsigned)(g < 1 ? 1 : (g > 16384 ? 16384 : g));

@@ -30,6 +30,20 @@ void slic_set_error(const char* fmt, ...);
 
 #define SLIC_LAUNCH_CHECK() SLIC_HIP_CHECK(hipGetLastError())
 
+// Raise `kernel`'s dynamic-LDS limit on the current device to at least `bytes`.  The limit is remembered per (device, kernel)
+// and only ever raised, so call it before every launch with the size about to be used.  SLIC_OK or SLIC_EHIP (+ slic_last_error).
+int slic_lds_limit(const void* kernel, size_t bytes);
+// compute units of the current device; 0 when no device answers
+int slic_device_cus(void);
+
+#define SLIC_LDS_LIMIT(kernel, bytes)                                  \
+  do {                                                                 \
+    int _rc = slic_lds_limit((const void*)(kernel), (size_t)(bytes));  \
+    if (_rc != SLIC_OK) return _rc;                                    \
+  } while (0)
+
+static inline hipStream_t S_(void* s) { return (hipStream_t)s; }
+
 static inline size_t slic_align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 static inline int64_t slic_cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 

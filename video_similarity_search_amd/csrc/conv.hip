@@ -780,12 +780,7 @@ template <int G, int STAGES, bool ILV = false, bool RT = false>
 static int launch_wgrad_dma(const SlicConvArgs& a, const float* dy, int ldy, unsigned dyb, float* slab, int per, int S,
                             hipStream_t st) {
   const size_t lds = (size_t)STAGES * (G + 1) * 32 * 64 * sizeof(float);
-  static bool attr_set = false;
-  if (!attr_set) {
-    SLIC_HIP_CHECK(hipFuncSetAttribute((const void*)conv_wgrad_dma_kernel<G, STAGES, ILV, RT>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr_set = true;
-  }
+  SLIC_LDS_LIMIT((conv_wgrad_dma_kernel<G, STAGES, ILV, RT>), lds);
   const int64_t total = slic_cdiv(a.nchunks, 16 * G) * slic_cdiv(a.N, 64) * S;
   conv_wgrad_dma_kernel<G, STAGES, ILV, RT><<<dim3((unsigned)total), dim3(256), lds, st>>>(a, dy, ldy, dyb, slab, per, S);
   SLIC_LAUNCH_CHECK();
@@ -983,7 +978,6 @@ __global__ void ncdhw_to_ndhwc_wpad(const float* __restrict__ x, int B, int C, i
 }
 
 // ------------------------------------ C ABI ------------------------------------------------
-static inline hipStream_t S_(void* s) { return (hipStream_t)s; }
 
 // ------------------------------------------------------------------------------------------
 // Winograd F(4, 3) along W for the 3 x 3 x 3, stride-1, pad-1 convolutions (layer1 / layer2: W = 56 / 28) — forward and,
@@ -1332,11 +1326,7 @@ template <int STAGES, bool WPAD, int TG>
 static int launch_wino(const SlicConvArgs& a, hipStream_t st, int splits = 1, float* slab = nullptr, int nfull = 0) {
   constexpr size_t ring = (size_t)STAGES * wino_stage_floats(TG) * sizeof(float), epi = (size_t)conv_epi_lds_floats(128, 64, 2 * TG) * sizeof(float);
   constexpr size_t lds = ring > epi ? ring : epi;
-  static bool attr_set = false;
-  if (!attr_set) {
-    SLIC_HIP_CHECK(hipFuncSetAttribute((const void*)conv_wino_kernel<STAGES, WPAD, TG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr_set = true;
-  }
+  SLIC_LDS_LIMIT((conv_wino_kernel<STAGES, WPAD, TG>), lds);
   const int64_t tiles = (a.M / a.Ws) * ((a.Ws + 3) / 4);
   const int gx = (int)slic_cdiv(tiles, 32 * TG);               // tile blocks
   const unsigned ny = (unsigned)(a.N / 64);
@@ -1664,12 +1654,7 @@ template <int BM, int BN, int WM, int WN>
 static int launch_gemm(const SlicConvArgs& a, hipStream_t st) {
   constexpr size_t ring = (size_t)2 * (BM + BN) * 32 * sizeof(float), epi = (size_t)conv_epi_lds_floats(BM, BN) * sizeof(float);
   constexpr size_t lds = ring > epi ? ring : epi;
-  static bool attr_set = false;
-  if (!attr_set) {
-    SLIC_HIP_CHECK(hipFuncSetAttribute((const void*)conv_gemm_kernel<BM, BN, WM, WN>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr_set = true;
-  }
+  SLIC_LDS_LIMIT((conv_gemm_kernel<BM, BN, WM, WN>), lds);
   dim3 grid((unsigned)slic_cdiv(a.M, BM), (unsigned)slic_cdiv(a.N, BN));
   conv_gemm_kernel<BM, BN, WM, WN><<<grid, dim3(256), lds, st>>>(a);
   SLIC_LAUNCH_CHECK();
@@ -1680,12 +1665,7 @@ template <int BM, int BN, int WM, int WN, int STAGES = 2, int KD = 32>
 static int launch_gemm_dma(const SlicConvArgs& a, hipStream_t st) {
   constexpr size_t ring = (size_t)STAGES * (BM + BN) * KD * sizeof(float), epi = (size_t)conv_epi_lds_floats(BM, BN) * sizeof(float);
   constexpr size_t lds = ring > epi ? ring : epi;
-  static bool attr_set = false;
-  if (!attr_set) {
-    SLIC_HIP_CHECK(hipFuncSetAttribute((const void*)conv_gemm_dma_kernel<BM, BN, WM, WN, STAGES, KD>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr_set = true;
-  }
+  SLIC_LDS_LIMIT((conv_gemm_dma_kernel<BM, BN, WM, WN, STAGES, KD>), lds);
   const unsigned gx = (unsigned)slic_cdiv(a.M, BM);
   // XCD-aware order (see the kernel body): the grid is rounded up to a multiple of 8 row blocks
   dim3 grid((gx + 7) / 8 * 8, (unsigned)slic_cdiv(a.N, BN));
@@ -1698,12 +1678,7 @@ template <int BM, int BN, int WM, int WN, int STAGES = 2, int KD = 32>
 static int launch_gemm_dma_tail(const SlicConvArgs& a, hipStream_t st, int nfull_rb, int splits, float* slab) {
   constexpr size_t ring = (size_t)STAGES * (BM + BN) * KD * sizeof(float), epi = (size_t)conv_epi_lds_floats(BM, BN) * sizeof(float);
   constexpr size_t lds = ring > epi ? ring : epi;
-  static bool attr_set = false;
-  if (!attr_set) {
-    SLIC_HIP_CHECK(hipFuncSetAttribute((const void*)conv_gemm_dma_tail_kernel<BM, BN, WM, WN, STAGES, KD>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr_set = true;
-  }
+  SLIC_LDS_LIMIT((conv_gemm_dma_tail_kernel<BM, BN, WM, WN, STAGES, KD>), lds);
   const int nrb = (int)slic_cdiv(a.M, BM), ny = (int)slic_cdiv(a.N, BN);
   const int nk = a.nchunks / (KD / 4);
   const int per = (nk + splits - 1) / splits;
@@ -1772,12 +1747,7 @@ template <int BM, int BN, int WM, int WN, int STAGES = 2, int KD = 32>
 static int launch_gemm_dma_multi(const SlicConvArgs* a, int n, hipStream_t st) {
   constexpr size_t ring = (size_t)STAGES * (BM + BN) * KD * sizeof(float), epi = (size_t)conv_epi_lds_floats(BM, BN) * sizeof(float);
   constexpr size_t lds = ring > epi ? ring : epi;
-  static bool attr_set = false;
-  if (!attr_set) {
-    SLIC_HIP_CHECK(hipFuncSetAttribute((const void*)conv_gemm_dma_multi_kernel<BM, BN, WM, WN, STAGES, KD>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr_set = true;
-  }
+  SLIC_LDS_LIMIT((conv_gemm_dma_multi_kernel<BM, BN, WM, WN, STAGES, KD>), lds);
   constexpr int xcd = 1;
   SlicConvArgsPack pk;
   unsigned gmax = 0;
@@ -1955,11 +1925,7 @@ extern "C" int slic_conv_wgrad_wino(const SlicConvArgs* a, const float* dy, int 
   hipStream_t st = S_(stream);
   constexpr int STAGES = 3;          // a 4-stage ring (80 KB, still two workgroups per CU) measured equal: the loss is not prefetch depth
   constexpr size_t lds = (size_t)STAGES * WW_STAGE_FLOATS * sizeof(float);
-  static bool attr_set = false;
-  if (!attr_set) {
-    SLIC_HIP_CHECK(hipFuncSetAttribute((const void*)conv_wgrad_wino_kernel<STAGES>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr_set = true;
-  }
+  SLIC_LDS_LIMIT(conv_wgrad_wino_kernel<STAGES>, lds);
   const int64_t total = (int64_t)9 * (a->Cs / 64) * (a->N / 64) * S;
   SLIC_REQUIRE(total < (1ll << 30), "slic_conv_wgrad_wino: grid too large");
   const unsigned gx = (unsigned)((total + 7) / 8 * 8);

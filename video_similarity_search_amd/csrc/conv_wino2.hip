@@ -1345,14 +1345,9 @@ size_t slic_conv_wino2_split_workspace_bytes(const SlicConvArgs* a, int nfull, i
 static int w2_persist_grid() {
   const char* e = getenv("SLIC_WINO2_PERSIST_GRID");
   if (e && atoi(e) >= 8) return atoi(e) / 8 * 8;
-  static int n = 0;
-  if (!n) {
-    int dev = 0;
-    hipDeviceProp_t pr;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&pr, dev) != hipSuccess) { (void)hipGetLastError(); return 256; }
-    n = pr.multiProcessorCount >= 8 ? pr.multiProcessorCount / 8 * 8 : 8;
-  }
-  return n;
+  const int cus = slic_device_cus();
+  if (!cus) return 256;                                       // no device: the host-side plan queries still answer
+  return cus >= 8 ? cus / 8 * 8 : 8;
 }
 
 // SLIC_WINO2_PERSIST: 0 = the one-block-per-workgroup kernel everywhere; 1 (default) = the whole tile blocks of a launch with at least two
@@ -1381,15 +1376,12 @@ static int w2_launch_persist(const SlicConvArgs* a, hipStream_t st, int nblocks,
   (void)lds;
   const bool loads = a->addend || a->mask_src || a->bwd_z || a->scale || a->shift;
   const dim3 grid((unsigned)w2_persist_grid());
-#define W2P_GO(L, C_) conv_wino2p_kernel<L, C_><<<grid, dim3(512), W2P_LDS_BYTES, st>>>(*a, nblocks, (int)ny)
-#define W2P_PICK(L)                                                                    \
-  do {                                                                                  \
-    if (a->Cs == 64) W2P_GO(L, 64); else if (a->Cs == 128) W2P_GO(L, 128);               \
-    else if (a->Cs == 256) W2P_GO(L, 256); else W2P_GO(L, 0);                            \
-  } while (0)
-  if (loads) W2P_PICK(true); else W2P_PICK(false);
+#define W2P_PICK(L) \
+  (a->Cs == 64 ? conv_wino2p_kernel<L, 64> : a->Cs == 128 ? conv_wino2p_kernel<L, 128> : a->Cs == 256 ? conv_wino2p_kernel<L, 256> : conv_wino2p_kernel<L, 0>)
+  const auto kern = loads ? W2P_PICK(true) : W2P_PICK(false);
 #undef W2P_PICK
-#undef W2P_GO
+  SLIC_LDS_LIMIT(kern, W2P_LDS_BYTES);
+  kern<<<grid, dim3(512), W2P_LDS_BYTES, st>>>(*a, nblocks, (int)ny);
   SLIC_LAUNCH_CHECK();
   return SLIC_OK;
 }
@@ -1401,16 +1393,7 @@ int slic_conv_wino2_launch(const SlicConvArgs* a, hipStream_t st, int nfull, flo
   if (rc) return rc;
   constexpr size_t lds = w2_lds_bytes();
   static_assert(lds <= 160 * 1024, "LDS");
-  static bool attr_set = false;
-  if (!attr_set) {
-    SLIC_HIP_CHECK(hipFuncSetAttribute((const void*)conv_wino2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-#define W2P_ATTR(L, C_) SLIC_HIP_CHECK(hipFuncSetAttribute((const void*)conv_wino2p_kernel<L, C_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)W2P_LDS_BYTES))
-    W2P_ATTR(false, 0); W2P_ATTR(false, 64); W2P_ATTR(false, 128); W2P_ATTR(false, 256);
-    W2P_ATTR(true, 0); W2P_ATTR(true, 64); W2P_ATTR(true, 128); W2P_ATTR(true, 256);
-#undef W2P_ATTR
-    SLIC_HIP_CHECK(hipFuncSetAttribute((const void*)conv_wino2_finish, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr_set = true;
-  }
+  SLIC_LDS_LIMIT(conv_wino2_kernel, lds);
   const int64_t tiles = (a->M / ((int64_t)a->Hs * a->Ws)) * ((a->Hs + 1) / 2) * ((a->Ws + 3) / 4);
   const int gx = (int)slic_cdiv(tiles, 64);
   const unsigned ny = (unsigned)(a->N / 64);
@@ -1441,6 +1424,7 @@ int slic_conv_wino2_launch(const SlicConvArgs* a, hipStream_t st, int nfull, flo
   const int tail = gx - nfull;
   conv_wino2_kernel<<<dim3((unsigned)((tail + 7) / 8 * 8), ny, (unsigned)pieces), dim3(512), lds, st>>>(*a, full, slab, nfull, tail);
   SLIC_LAUNCH_CHECK();
+  SLIC_LDS_LIMIT(conv_wino2_finish, lds);
   conv_wino2_finish<<<dim3((unsigned)tail, ny), dim3(512), lds, st>>>(*a, full, slab, nfull, pieces);
   SLIC_LAUNCH_CHECK();
   return SLIC_OK;
@@ -1903,11 +1887,7 @@ extern "C" int slic_conv_wgrad_wino2(const SlicConvArgs* a, const float* dy, int
   hipStream_t st = (hipStream_t)stream;
   constexpr size_t lds = (size_t)WB_STAGES * WB_STAGE_BYTES;
   static_assert(lds <= 160 * 1024, "LDS");
-  static bool attr_set = false;
-  if (!attr_set) {
-    SLIC_HIP_CHECK(hipFuncSetAttribute((const void*)conv_wgrad_wino2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr_set = true;
-  }
+  SLIC_LDS_LIMIT(conv_wgrad_wino2_kernel, lds);
   const int64_t total = (int64_t)3 * (a->Cs / 64) * (a->N / 64) * S;
   SLIC_REQUIRE(total < (1ll << 30), "slic_conv_wgrad_wino2: grid too large");
   const unsigned gx = (unsigned)((total + 7) / 8 * 8);

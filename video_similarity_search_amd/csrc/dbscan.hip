@@ -465,7 +465,6 @@ __global__ __launch_bounds__(256) void db_label_border(const int* __restrict__ b
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------
-static inline hipStream_t S_(void* s) { return (hipStream_t)s; }
 
 struct DbLayout {
   unsigned long long* stats; int* meta; double* inv; float* Xn; float* Xcb; int* cnt;
@@ -512,28 +511,13 @@ static int db_mark(hipStream_t st, int i) {
   return SLIC_OK;
 }
 
-static int db_lds_attr() {
-  static bool done = false;
-  if (done) return SLIC_OK;
-  constexpr int LDS = (4 * DB_B * DB_BK) * 4 + 4 * DB_PC * 64 * 4 + (DB_B + DB_SLICE + 4) * 4;
-#define DB_ATTR(NK) \
-  SLIC_HIP_CHECK(hipFuncSetAttribute((const void*)db_tiles<NK, DB_COUNT>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS)); \
-  SLIC_HIP_CHECK(hipFuncSetAttribute((const void*)db_tiles<NK, DB_LINK>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS)); \
-  SLIC_HIP_CHECK(hipFuncSetAttribute((const void*)db_tiles<NK, DB_BORDER>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-  DB_ATTR(4) DB_ATTR(8) DB_ATTR(12) DB_ATTR(16)
-#undef DB_ATTR
-  done = true;
-  return SLIC_OK;
-}
-
 template <int MODE>
-static void db_launch_tiles(int NK, dim3 grid, size_t lds, hipStream_t st, const DbArgs& a) {
-  switch (NK) {
-    case 4: db_tiles<4, MODE><<<grid, dim3(256), lds, st>>>(a); break;
-    case 8: db_tiles<8, MODE><<<grid, dim3(256), lds, st>>>(a); break;
-    case 12: db_tiles<12, MODE><<<grid, dim3(256), lds, st>>>(a); break;
-    default: db_tiles<16, MODE><<<grid, dim3(256), lds, st>>>(a); break;
-  }
+static int db_launch_tiles(int NK, dim3 grid, size_t lds, hipStream_t st, const DbArgs& a) {
+  const auto kern = NK == 4 ? db_tiles<4, MODE> : NK == 8 ? db_tiles<8, MODE> : NK == 12 ? db_tiles<12, MODE> : db_tiles<16, MODE>;
+  SLIC_LDS_LIMIT(kern, lds);
+  kern<<<grid, dim3(256), lds, st>>>(a);
+  SLIC_LAUNCH_CHECK();
+  return SLIC_OK;
 }
 
 extern "C" int slic_dbscan_cosine(const float* X, int64_t N, int ldx, int D, double eps, int min_samples, int32_t* labels,
@@ -552,7 +536,6 @@ extern "C" int slic_dbscan_cosine(const float* X, int64_t N, int ldx, int D, dou
   DbLayout L;
   db_layout(workspace, N, Dp, &L);
   int* cnt = counts ? counts : L.cnt;
-  { int r = db_lds_attr(); if (r) return r; }
   const char* tenv = getenv("SLIC_DBSCAN_TIMING");
   db_ev_on = tenv && tenv[0] == '1';
   if (db_ev_on)
@@ -590,8 +573,7 @@ extern "C" int slic_dbscan_cosine(const float* X, int64_t N, int ldx, int D, dou
   constexpr size_t LDS = (4 * DB_B * DB_BK) * 4 + 4 * DB_PC * 64 * 4 + (DB_B + DB_SLICE + 4) * 4;
 
   a.Xcb = L.Xn;
-  db_launch_tiles<DB_COUNT>(NK, grid, LDS, st, a);
-  SLIC_LAUNCH_CHECK();
+  { int r = db_launch_tiles<DB_COUNT>(NK, grid, LDS, st, a); if (r) return r; }
   { int r = db_mark(st, 2); if (r) return r; }
   db_compact<<<1, DB_SCAN_T, 0, st>>>(cnt, n, min_samples, is_core, labels, L.core_idx, L.border_idx, L.meta);
   SLIC_LAUNCH_CHECK();
@@ -600,8 +582,7 @@ extern "C" int slic_dbscan_cosine(const float* X, int64_t N, int ldx, int D, dou
   SLIC_LAUNCH_CHECK();
   { int r = db_mark(st, 3); if (r) return r; }
   a.Xcb = L.Xcb;
-  db_launch_tiles<DB_LINK>(NK, grid, LDS, st, a);
-  SLIC_LAUNCH_CHECK();
+  { int r = db_launch_tiles<DB_LINK>(NK, grid, LDS, st, a); if (r) return r; }
   { int r = db_mark(st, 4); if (r) return r; }
   const int gn = (int)std::min<int64_t>(4096, slic_cdiv(n, 256));
   db_compress<<<gn, 256, 0, st>>>(L.parent, L.meta);
@@ -612,8 +593,7 @@ extern "C" int slic_dbscan_cosine(const float* X, int64_t N, int ldx, int D, dou
   SLIC_LAUNCH_CHECK();
   { int r = db_mark(st, 5); if (r) return r; }
   // border rows: only the candidates the compaction listed (none at min_samples <= 2: every workgroup leaves at once)
-  db_launch_tiles<DB_BORDER>(NK, grid, LDS, st, a);
-  SLIC_LAUNCH_CHECK();
+  { int r = db_launch_tiles<DB_BORDER>(NK, grid, LDS, st, a); if (r) return r; }
   db_label_border<<<gn, 256, 0, st>>>(L.best, L.cid, L.meta, L.border_idx, labels);
   SLIC_LAUNCH_CHECK();
   { int r = db_mark(st, 6); if (r) return r; }

@@ -1940,11 +1940,10 @@ __global__ __launch_bounds__(KPP_ST) void kpp_select_batch(const double* __restr
 }
 
 // ------------------------------------ C ABI ------------------------------------------------
-static inline hipStream_t S(void* s) { return (hipStream_t)s; }
 
 extern "C" int slic_kmeans_cnorm(const float* C, int K, int D, int ldc, float* cnorm, void* stream) {
   SLIC_REQUIRE(C && cnorm && K > 0 && D > 0 && ldc >= D, "slic_kmeans_cnorm: bad args");
-  km_cnorm<<<dim3((unsigned)slic_cdiv(K, 64)), dim3(64), 0, S(stream)>>>(C, K, D, ldc, cnorm);
+  km_cnorm<<<dim3((unsigned)slic_cdiv(K, 64)), dim3(64), 0, S_(stream)>>>(C, K, D, ldc, cnorm);
   SLIC_LAUNCH_CHECK();
   return SLIC_OK;
 }
@@ -1987,10 +1986,10 @@ extern "C" int slic_kmeans_assign(const float* X, int64_t N, int D, int ldx, con
   float* pscore = w.take<float>((size_t)slic_cdiv(K, 32) * N);
   int32_t* pidx = w.take<int32_t>((size_t)slic_cdiv(K, 32) * N);
   dim3 grid((unsigned)slic_cdiv(N, KM_BP), (unsigned)G);
-  if (nct == 2) km_assign_partial<2><<<grid, dim3(256), 0, S(stream)>>>(X, N, D, ldx, C, K, ldc, cnorm, pscore, pidx);
-  else km_assign_partial<4><<<grid, dim3(256), 0, S(stream)>>>(X, N, D, ldx, C, K, ldc, cnorm, pscore, pidx);
+  if (nct == 2) km_assign_partial<2><<<grid, dim3(256), 0, S_(stream)>>>(X, N, D, ldx, C, K, ldc, cnorm, pscore, pidx);
+  else km_assign_partial<4><<<grid, dim3(256), 0, S_(stream)>>>(X, N, D, ldx, C, K, ldc, cnorm, pscore, pidx);
   SLIC_LAUNCH_CHECK();
-  km_combine<false><<<dim3((unsigned)slic_cdiv(N, 256)), dim3(256), 0, S(stream)>>>(
+  km_combine<false><<<dim3((unsigned)slic_cdiv(N, 256)), dim3(256), 0, S_(stream)>>>(
       pscore, pidx, G, N, K, labels, labels_old, n_changed, best_score, nullptr);
   SLIC_LAUNCH_CHECK();
   return SLIC_OK;
@@ -2001,11 +2000,7 @@ static int launch_assign_dma(const float* Xp, int64_t N, int D, int ldx, const f
                              const float* cnorm, float* pscore, int32_t* pidx, hipStream_t st, int32_t* z0 = nullptr,
                              int32_t* z1 = nullptr) {
   const size_t lds = (size_t)STAGES * (BP + NCT * 32) * KM_BK * sizeof(float);
-  static bool attr_set = false;
-  if (!attr_set) {
-    SLIC_HIP_CHECK(hipFuncSetAttribute((const void*)km_assign_dma<BP, NCT, WC, STAGES>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr_set = true;
-  }
+  SLIC_LDS_LIMIT((km_assign_dma<BP, NCT, WC, STAGES>), lds);
   dim3 grid((unsigned)slic_cdiv(N, BP), (unsigned)slic_cdiv(K, NCT * 32));
   km_assign_dma<BP, NCT, WC, STAGES><<<grid, dim3(256), lds, st>>>(Xp, N, D, ldx, Cp, K, ldc, cnorm, pscore, pidx, z0, z1);
   SLIC_LAUNCH_CHECK();
@@ -2016,7 +2011,7 @@ extern "C" int slic_kmeans_permute_k8(const float* X, int64_t N, int D, int ldx,
   SLIC_REQUIRE(X && Xp && X != Xp && N > 0 && D > 0 && D % 8 == 0 && ldx % 4 == 0 && ldxp % 4 == 0 && ldx >= D && ldxp >= D,
                "slic_kmeans_permute_k8: need D %% 8 == 0 and 16-byte aligned rows");
   const int64_t tot = N * (D / 8);
-  km_permute_k8<<<dim3((unsigned)slic_cdiv(tot, 256)), dim3(256), 0, S(stream)>>>(X, N, D / 8, ldx, Xp, ldxp);
+  km_permute_k8<<<dim3((unsigned)slic_cdiv(tot, 256)), dim3(256), 0, S_(stream)>>>(X, N, D / 8, ldx, Xp, ldxp);
   SLIC_LAUNCH_CHECK();
   return SLIC_OK;
 }
@@ -2039,14 +2034,13 @@ static int km_assign_perm_impl(const float* Xp, int64_t N, int D, int ldx, const
   SlicCarver w(workspace);
   float* pscore = w.take<float>((size_t)slic_cdiv(K, 32) * N);
   int32_t* pidx = w.take<int32_t>((size_t)slic_cdiv(K, 32) * N);
-  hipStream_t st = S(stream);
+  hipStream_t st = S_(stream);
   // Centroids in registers (km_assign_creg) when a 128-centroid block per workgroup wastes little (K = 500 -> 512) and the
   // blocks x slices grid can cover the device: one residency round of 1-workgroup-per-CU workgroups.
-  static int cus = 0;
+  const int cus = slic_device_cus();
   if (!cus) {
-    int dev = 0;
-    SLIC_HIP_CHECK(hipGetDevice(&dev));
-    SLIC_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    slic_set_error("slic_kmeans_assign_perm: cannot query the device's compute units");
+    return SLIC_EHIP;
   }
   const int ncb = (int)slic_cdiv(K, 128);
   const int64_t tiles = slic_cdiv(N, 128);
@@ -2062,17 +2056,10 @@ static int km_assign_perm_impl(const float* Xp, int64_t N, int D, int ldx, const
                     (slic_cdiv(tiles, slices) * 128 + 128) * (int64_t)ldx * 4 < (1ll << 31);        // slice inside one resource
   if (creg) {
     const size_t lds = (size_t)4 * 128 * KM_BK * sizeof(float) + 4 * 128 * 2 * sizeof(float);     // the ring + the tile's four pair lists
-    static bool attr_set = false;
-    if (!attr_set) {
-      SLIC_HIP_CHECK(hipFuncSetAttribute((const void*)km_assign_creg<16, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      SLIC_HIP_CHECK(hipFuncSetAttribute((const void*)km_assign_creg<8, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      SLIC_HIP_CHECK(hipFuncSetAttribute((const void*)km_assign_creg<4, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      attr_set = true;
-    }
     dim3 grid((unsigned)slices, (unsigned)ncb);
-    if (D > 256) km_assign_creg<16, 4><<<grid, dim3(256), lds, st>>>(Xp, N, D, ldx, Cp, K, ldc, cnorm, pscore, pidx, z0, z1);
-    else if (D > 128) km_assign_creg<8, 4><<<grid, dim3(256), lds, st>>>(Xp, N, D, ldx, Cp, K, ldc, cnorm, pscore, pidx, z0, z1);
-    else km_assign_creg<4, 4><<<grid, dim3(256), lds, st>>>(Xp, N, D, ldx, Cp, K, ldc, cnorm, pscore, pidx, z0, z1);
+    const auto kern = D > 256 ? km_assign_creg<16, 4> : D > 128 ? km_assign_creg<8, 4> : km_assign_creg<4, 4>;
+    SLIC_LDS_LIMIT(kern, lds);
+    kern<<<grid, dim3(256), lds, st>>>(Xp, N, D, ldx, Cp, K, ldc, cnorm, pscore, pidx, z0, z1);
     SLIC_LAUNCH_CHECK();
     G = ncb;                                                   // one list per 128-centroid block
   } else {
@@ -2141,18 +2128,13 @@ static int km_accumulate_impl(const float* X, int64_t N, int D, int ldx, const i
   int32_t* cnt = w.take<int32_t>(K);
   int32_t* done = w.take<int32_t>(K);        // [0]: km_accumulate_average's counter (km_accumulate_done_counter)
   int32_t* order = w.take<int32_t>((size_t)N);
-  hipStream_t st = S(stream);
+  hipStream_t st = S_(stream);
   SLIC_REQUIRE(K <= 16384, "slic_kmeans_accumulate: K > 16384");
   if (km_small_shard(N, D, ldx) && !fin && ((uintptr_t)labels % 16) == 0) {
     // small shard: the workgroups find their rows themselves (no histogram, no counting sort)
     const int seg = (int)slic_cdiv(slic_cdiv(N, 8), 16) * 16;
     const size_t lds = (size_t)8 * seg * sizeof(unsigned short);
-    static size_t lds_set = 0;
-    if (lds > lds_set) {
-      SLIC_HIP_CHECK(hipFuncSetAttribute((const void*)km_scan_accumulate<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(64 * 1024)));
-      SLIC_HIP_CHECK(hipFuncSetAttribute((const void*)km_scan_accumulate<double>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(64 * 1024)));
-      lds_set = 64 * 1024;
-    }
+    if (lds > 48 * 1024) SLIC_LDS_LIMIT(km_scan_accumulate<TOut>, lds);
     km_scan_accumulate<TOut><<<dim3(K), dim3(512), lds, st>>>(X, (int)N, D, ldx, labels, seg, sums, counts, n_changed, nch_out, xperm);
     SLIC_LAUNCH_CHECK();
     return SLIC_OK;
@@ -2163,13 +2145,7 @@ static int km_accumulate_impl(const float* X, int64_t N, int D, int ldx, const i
   }
   const int use_wcnt = (size_t)K * 4 * (2 + KM_SB / 64) <= 96 * 1024;
   const size_t lds_place = (size_t)K * 4 * (use_wcnt ? 2 + KM_SB / 64 : 2);
-  if (lds_place > 48 * 1024) {
-    static size_t lds_set = 0;
-    if (lds_place > lds_set) {
-      SLIC_HIP_CHECK(hipFuncSetAttribute((const void*)km_place, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_place));
-      lds_set = lds_place;
-    }
-  }
+  if (lds_place > 48 * 1024) SLIC_LDS_LIMIT(km_place, lds_place);
   km_place<<<dim3(nblk), dim3(KM_SB), lds_place, st>>>(labels, N, K, bc, nblk, cnt, order, use_wcnt);
   SLIC_LAUNCH_CHECK();
   if constexpr (sizeof(TOut) == 4) {
@@ -2202,7 +2178,7 @@ extern "C" int slic_kmeans_combine_shards(const float* ps, const float* pc, int6
   SLIC_REQUIRE(ps && pc && sums && counts && n_shards > 0 && K > 0 && D > 0 && shard_stride > 0,
                "slic_kmeans_combine_shards: bad args");
   const int64_t KD = (int64_t)K * D;
-  km_combine_shards<<<dim3((unsigned)slic_cdiv(KD, 256)), dim3(256), 0, S(stream)>>>(ps, pc, shard_stride, n_shards, K, D, sums, counts);
+  km_combine_shards<<<dim3((unsigned)slic_cdiv(KD, 256)), dim3(256), 0, S_(stream)>>>(ps, pc, shard_stride, n_shards, K, D, sums, counts);
   SLIC_LAUNCH_CHECK();
   return SLIC_OK;
 }
@@ -2212,7 +2188,7 @@ extern "C" int slic_kmeans_dist_to_assigned(const float* X, int64_t N, int D, in
                                             float* dist, void* stream) {
   SLIC_REQUIRE(X && C && labels && dist && N > 0 && D > 0 && D % 4 == 0 && ldx % 4 == 0 && ldc % 4 == 0,
                "slic_kmeans_dist_to_assigned: bad args (D %% 4 == 0 required)");
-  km_dist_to_assigned<<<dim3((unsigned)slic_cdiv(N, 256)), dim3(256), 0, S(stream)>>>(X, N, D, ldx, C, ldc, labels, dist);
+  km_dist_to_assigned<<<dim3((unsigned)slic_cdiv(N, 256)), dim3(256), 0, S_(stream)>>>(X, N, D, ldx, C, ldc, labels, dist);
   SLIC_LAUNCH_CHECK();
   return SLIC_OK;
 }
@@ -2223,9 +2199,9 @@ extern "C" size_t slic_sum_f32_to_f64_workspace_bytes(int64_t N) {
 extern "C" int slic_sum_f32_to_f64(const float* v, int64_t N, double* out, void* workspace, void* stream) {
   SLIC_REQUIRE(v && out && workspace && N > 0, "slic_sum_f32_to_f64: bad args");
   const int64_t nb = slic_cdiv(N, 256);
-  sum_blocks_f64<<<dim3((unsigned)nb), dim3(256), 0, S(stream)>>>(v, N, (double*)workspace);
+  sum_blocks_f64<<<dim3((unsigned)nb), dim3(256), 0, S_(stream)>>>(v, N, (double*)workspace);
   SLIC_LAUNCH_CHECK();
-  sum_serial_f64<<<dim3(1), dim3(64), 0, S(stream)>>>((const double*)workspace, nb, out);
+  sum_serial_f64<<<dim3(1), dim3(64), 0, S_(stream)>>>((const double*)workspace, nb, out);
   SLIC_LAUNCH_CHECK();
   return SLIC_OK;
 }
@@ -2233,7 +2209,7 @@ extern "C" int slic_sum_f32_to_f64(const float* v, int64_t N, double* out, void*
 extern "C" int slic_kmeans_select_far(float* dist, int64_t N, int n_sel, int32_t* far_idx,
                                       float* far_dist, void* stream) {
   SLIC_REQUIRE(dist && far_idx && far_dist && N > 0 && n_sel > 0, "slic_kmeans_select_far: bad args");
-  km_select_far<<<dim3(1), dim3(1024), 0, S(stream)>>>(dist, N, n_sel, far_idx, far_dist);
+  km_select_far<<<dim3(1), dim3(1024), 0, S_(stream)>>>(dist, N, n_sel, far_idx, far_dist);
   SLIC_LAUNCH_CHECK();
   return SLIC_OK;
 }
@@ -2243,7 +2219,7 @@ extern "C" int slic_kmeans_apply_relocation(const float* xfar, int ldf, const in
                                             float* counts, void* stream) {
   SLIC_REQUIRE(xfar && old_ids && new_ids && sums && counts && n > 0 && D > 0 && ldf >= D,
                "slic_kmeans_apply_relocation: bad args");
-  km_apply_relocation<<<dim3(1), dim3(256), 0, S(stream)>>>(xfar, ldf, old_ids, new_ids, n, D, sums, counts);
+  km_apply_relocation<<<dim3(1), dim3(256), 0, S_(stream)>>>(xfar, ldf, old_ids, new_ids, n, D, sums, counts);
   SLIC_LAUNCH_CHECK();
   return SLIC_OK;
 }
@@ -2257,7 +2233,7 @@ extern "C" int slic_kmeans_finalize(const float* C_old, const float* sums, const
   SLIC_REQUIRE(C_new != sums && C_new != C_old, "slic_kmeans_finalize: C_new must not alias");
   SLIC_REQUIRE(D <= 8192, "slic_kmeans_finalize: D > 8192");
   SLIC_REQUIRE(!C_new_perm || D % 8 == 0, "slic_kmeans_finalize: C_new_perm needs D %% 8 == 0");
-  hipStream_t st = S(stream);
+  hipStream_t st = S_(stream);
   const size_t lds = ((size_t)D + D / 4 + 4) * sizeof(float);
   km_average<float, false><<<dim3(K), dim3(128), lds, st>>>(sums, counts, 0, 1, nullptr, nullptr, C_old, K, D, C_new, shift,
                                                             cnorm_new, C_new_perm, spherical);
@@ -2333,7 +2309,7 @@ extern "C" int slic_kmeans_lloyd_global(const void* parts, int parts_f64, int64_
   SLIC_REQUIRE(C_new != sums && C_new != C_old, "slic_kmeans_lloyd_global: C_new must not alias");
   SLIC_REQUIRE(D <= 8192, "slic_kmeans_lloyd_global: D > 8192");
   SLIC_REQUIRE(!Cp_new || D % 8 == 0, "slic_kmeans_lloyd_global: Cp_new needs D %% 8 == 0");
-  hipStream_t st = S(stream);
+  hipStream_t st = S_(stream);
   const size_t lds = ((size_t)D + D / 4 + 4) * sizeof(float);
   if (parts_f64) {
     const double* p = (const double*)parts;
@@ -2359,9 +2335,9 @@ extern "C" int slic_col_stats(const float* X, int64_t N, int D, int ldx, double*
                               double* col_sumsq, void* workspace, void* stream) {
   SLIC_REQUIRE(X && col_sum && col_sumsq && workspace && N > 0 && D > 0 && ldx >= D, "slic_col_stats: bad args");
   const int nseg = (int)slic_cdiv(N, 1024);
-  col_stats_seg<<<dim3((unsigned)slic_cdiv(D, 64), nseg), dim3(64), 0, S(stream)>>>(X, N, D, ldx, (double*)workspace);
+  col_stats_seg<<<dim3((unsigned)slic_cdiv(D, 64), nseg), dim3(64), 0, S_(stream)>>>(X, N, D, ldx, (double*)workspace);
   SLIC_LAUNCH_CHECK();
-  col_stats_fin<<<dim3((unsigned)slic_cdiv(D, 64)), dim3(64), 0, S(stream)>>>((const double*)workspace, nseg, D, col_sum, col_sumsq);
+  col_stats_fin<<<dim3((unsigned)slic_cdiv(D, 64)), dim3(64), 0, S_(stream)>>>((const double*)workspace, nseg, D, col_sum, col_sumsq);
   SLIC_LAUNCH_CHECK();
   return SLIC_OK;
 }
@@ -2371,14 +2347,14 @@ extern "C" int slic_sub_rowvec(const float* X, int64_t N, int D, int ldx, const 
   SLIC_REQUIRE(X && v && out && N > 0 && D > 0 && D % 4 == 0 && ldx % 4 == 0 && ldo % 4 == 0,
                "slic_sub_rowvec: bad args (D %% 4 == 0 required)");
   const int64_t tot = N * (D / 4);
-  sub_rowvec<<<dim3((unsigned)slic_cdiv(tot, 256)), dim3(256), 0, S(stream)>>>(X, N, D / 4, ldx, v, out, ldo);
+  sub_rowvec<<<dim3((unsigned)slic_cdiv(tot, 256)), dim3(256), 0, S_(stream)>>>(X, N, D / 4, ldx, v, out, ldo);
   SLIC_LAUNCH_CHECK();
   return SLIC_OK;
 }
 
 extern "C" int slic_l2norm_rows(const float* X, int64_t N, int D, int ldx, float* out, int ldo, void* stream) {
   SLIC_REQUIRE(X && out && N > 0 && D > 0 && ldx >= D && ldo >= D, "slic_l2norm_rows: bad args");
-  l2norm_rows<<<dim3((unsigned)slic_cdiv(N, 4)), dim3(256), 0, S(stream)>>>(X, N, D, ldx, out, ldo);
+  l2norm_rows<<<dim3((unsigned)slic_cdiv(N, 4)), dim3(256), 0, S_(stream)>>>(X, N, D, ldx, out, ldo);
   SLIC_LAUNCH_CHECK();
   return SLIC_OK;
 }
@@ -2393,9 +2369,9 @@ extern "C" int slic_kmeanspp_step(const float* X, int64_t N, int D, int ldx, con
   SLIC_REQUIRE(T >= 1 && T <= PP_TMAX && D % 4 == 0 && ldx % 4 == 0 && (size_t)T * D * 4 <= 64 * 1024,
                "slic_kmeanspp_step: need 1 <= T <= %d, D %% 4 == 0, T*D*4 <= 64 KiB", PP_TMAX);
   const int64_t nblk = slic_cdiv(N, 256);
-  kpp_dist<<<dim3((unsigned)nblk), dim3(256), (size_t)T * D * 4, S(stream)>>>(X, N, D, ldx, cand, T, closest, newdist, (double*)workspace);
+  kpp_dist<<<dim3((unsigned)nblk), dim3(256), (size_t)T * D * 4, S_(stream)>>>(X, N, D, ldx, cand, T, closest, newdist, (double*)workspace);
   SLIC_LAUNCH_CHECK();
-  kpp_pot<<<dim3(T), dim3(256), 0, S(stream)>>>((const double*)workspace, nblk, T, pot);
+  kpp_pot<<<dim3(T), dim3(256), 0, S_(stream)>>>((const double*)workspace, nblk, T, pot);
   SLIC_LAUNCH_CHECK();
   return SLIC_OK;
 }
@@ -2413,7 +2389,7 @@ extern "C" int slic_kmeanspp_run(const float* X, int64_t N, int D, int ldx, int 
   SLIC_REQUIRE(X && uniforms && idx_out && workspace, "slic_kmeanspp_run: null pointer");
   SLIC_REQUIRE(N > 0 && K > 0 && K <= N && first >= 0 && first < N && T >= 1 && T <= PP_TMAX && D % 4 == 0 && ldx % 4 == 0 &&
                (size_t)T * D * 4 <= 48 * 1024, "slic_kmeanspp_run: need 1 <= T <= %d, D %% 4 == 0, T*D*4 <= 48 KiB", PP_TMAX);
-  hipStream_t st = S(stream);
+  hipStream_t st = S_(stream);
   const int64_t nblk = slic_cdiv(N, KPP_CH);
   SlicCarver w(workspace);
   float* nd = w.take<float>((size_t)2 * T * N);
@@ -2425,13 +2401,7 @@ extern "C" int slic_kmeanspp_run(const float* X, int64_t N, int D, int ldx, int 
   // matrix-pipe distances when the caller has the k-permuted copy and the row norms (and 32-bit offsets reach every row)
   const bool mfma = Xp && xnorm && D % 8 == 0 && (int64_t)N * ldx * 4 < (1ll << 31);
   const size_t lds_m = (size_t)2 * (128 + 32) * KM_BK * sizeof(float);
-  if (mfma) {
-    static bool attr_set = false;
-    if (!attr_set) {
-      SLIC_HIP_CHECK(hipFuncSetAttribute((const void*)kpp_dist_mfma, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_m));
-      attr_set = true;
-    }
-  }
+  if (mfma) SLIC_LDS_LIMIT(kpp_dist_mfma, lds_m);
   const unsigned nblk_m = (unsigned)slic_cdiv(N, 128);
   // centre 0: one candidate (the uniformly drawn row), no closest yet
   SLIC_HIP_CHECK(hipMemcpyAsync(cand, &first, sizeof(int32_t), hipMemcpyHostToDevice, st));
@@ -2471,7 +2441,7 @@ extern "C" int slic_kmeanspp_run_batch(const float* Xp, const float* xnorm, int6
   SLIC_REQUIRE(N > 0 && K > 0 && K <= N && R >= 1 && T >= 1 && T <= PP_TMAX && R * T <= 160 && D % 8 == 0 && ldx % 4 == 0 &&
                (int64_t)N * ldx * 4 < (1ll << 31), "slic_kmeanspp_run_batch: need 1 <= T <= %d, R * T <= 160, D %% 8 == 0, N * ldx * 4 < 2 GiB", PP_TMAX);
   for (int r = 0; r < R; ++r) SLIC_REQUIRE(firsts[r] >= 0 && firsts[r] < N, "slic_kmeanspp_run_batch: firsts[%d] out of range", r);
-  hipStream_t st = S(stream);
+  hipStream_t st = S_(stream);
   const int64_t nblk = slic_cdiv(N, KPP_CH);
   SlicCarver w(workspace);
   float* nd = w.take<float>((size_t)2 * R * T * N);
@@ -2487,12 +2457,7 @@ extern "C" int slic_kmeanspp_run_batch(const float* Xp, const float* xnorm, int6
     const size_t lds = (size_t)2 * (128 + 32 * ng) * KM_BK * sizeof(float);
 #define KPP_BATCH(NG)                                                                                                              \
     {                                                                                                                              \
-      static bool attr_set = false;                                                                                                \
-      if (!attr_set) {                                                                                                             \
-        SLIC_HIP_CHECK(hipFuncSetAttribute((const void*)kpp_dist_mfma_batch<NG>, hipFuncAttributeMaxDynamicSharedMemorySize,     \
-                                           (int)((size_t)2 * (128 + 32 * NG) * KM_BK * sizeof(float))));                           \
-        attr_set = true;                                                                                                           \
-      }                                                                                                                            \
+      SLIC_LDS_LIMIT(kpp_dist_mfma_batch<NG>, lds);                                                                                \
       kpp_dist_mfma_batch<NG><<<dim3(nblk_m), dim3(256), lds, st>>>(Xp, xnorm, N, D, ldx, cand, RT, Tc, Tprev, prev, sel, cur,     \
                                                                    bpart, nblk);                                                   \
     }
@@ -2536,11 +2501,11 @@ extern "C" int slic_cumsum_search(const float* v, int64_t N, const double* vals,
                                   int32_t* idx_out, void* workspace, void* stream) {
   SLIC_REQUIRE(v && vals && idx_out && workspace && N > 0 && T > 0, "slic_cumsum_search: bad args");
   const int64_t nc = slic_cdiv(N, 1024);
-  cs_chunk_sums<<<dim3((unsigned)nc), dim3(256), 0, S(stream)>>>(v, N, (double*)workspace);
+  cs_chunk_sums<<<dim3((unsigned)nc), dim3(256), 0, S_(stream)>>>(v, N, (double*)workspace);
   SLIC_LAUNCH_CHECK();
-  cs_scan_chunks<<<dim3(1), dim3(64), 0, S(stream)>>>((double*)workspace, nc);
+  cs_scan_chunks<<<dim3(1), dim3(64), 0, S_(stream)>>>((double*)workspace, nc);
   SLIC_LAUNCH_CHECK();
-  cs_search<<<dim3((unsigned)slic_cdiv(T, 4)), dim3(256), 0, S(stream)>>>(v, N, (const double*)workspace, nc, vals, T, idx_out);
+  cs_search<<<dim3((unsigned)slic_cdiv(T, 4)), dim3(256), 0, S_(stream)>>>(v, N, (const double*)workspace, nc, vals, T, idx_out);
   SLIC_LAUNCH_CHECK();
   return SLIC_OK;
 }

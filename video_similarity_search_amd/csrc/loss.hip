@@ -487,8 +487,6 @@ __global__ void triplet_select_k_kernel(const float* __restrict__ Dm, const int6
   }
 }
 
-static inline hipStream_t S_(void* s) { return (hipStream_t)s; }
-
 extern "C" int slic_triplet_select_k(const float* dist, const int64_t* labels, int n, const int32_t* anchors, const int32_t* positives, int P,
                                      float margin, int K, const float* u, int32_t* negatives, int32_t* status, void* stream) {
   SLIC_REQUIRE(dist && labels && anchors && positives && negatives && u && status && n > 1 && P > 0 && K >= 1 && K <= TSK_MAX,

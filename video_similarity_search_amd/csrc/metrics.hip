@@ -32,8 +32,6 @@
 enum { CM_R = 0, CM_C = 1, CM_STATUS = 2, CM_NMETA = 16 };
 enum { CM_P_MI = 0, CM_P_HT = 1, CM_P_HP = 2, CM_P_EMI = 3 };
 
-static inline hipStream_t S_(void* s) { return (hipStream_t)s; }
-
 __global__ __launch_bounds__(CM_T) void cm_keys(const int32_t* __restrict__ labels, int N, uint32_t* __restrict__ keys) {
   const int i = blockIdx.x * CM_T + threadIdx.x;
   if (i < N) keys[i] = (uint32_t)labels[i] ^ 0x80000000u;

@@ -267,8 +267,6 @@ __global__ __launch_bounds__(1024) void nce_fused_bwd(const float* __restrict__ 
   }
 }
 
-static inline hipStream_t S_(void* s) { return (hipStream_t)s; }
-
 extern "C" int slic_nce_scores_fwd(const float* bank, const int64_t* idx, const float* f, int B, int K1, int D,
                                    float T, float* out, float* gathered, void* stream) {
   SLIC_REQUIRE(bank && idx && f && out && B > 0 && K1 > 0 && D > 0 && D % 4 == 0 && T > 0.f,

@@ -1182,8 +1182,6 @@ __global__ void pairwise_euclid_kernel(const float* __restrict__ X, int Nx, cons
   out[e] = sqrtf(a);
 }
 
-static inline hipStream_t S_(void* s) { return (hipStream_t)s; }
-
 extern "C" int slic_normalize_rows(const float* X, int64_t N, int D, int ldx, float* out, void* stream) {
   SLIC_REQUIRE(X && out && N > 0 && D > 0 && ldx >= D, "slic_normalize_rows: bad args");
   normalize_rows_sklearn<<<dim3((unsigned)slic_cdiv(N, 4)), dim3(256), 0, S_(stream)>>>(X, N, D, ldx, out);
@@ -1264,22 +1262,7 @@ extern "C" size_t slic_cosine_topk_workspace_bytes(int Nq, int Ng, int k) {
 // the streaming path: per-(query, slice) lists in LDS + merge.  qmap / nq_dev (device memory; both or neither): query slot q of [0, *nq_dev)
 // is row qmap[q] of Qn and its result goes to output row qmap[q] — the exact fallback of the collect path; Nq then bounds the slot count.
 // The streaming launch (topk_stream) and the collect path's sample pass (topk_collect) launch the SAME topk_partial_qreg instantiations with
-// different dynamic-LDS sizes.  Two per-call-site "largest size set so far" caches could lower the attribute under each other's feet (the
-// smaller call site overwriting the larger one's value: ADVICE round 5); the attribute is therefore set ONCE, for every instantiation, to
-// the device maximum (160 KB) — every launch size of either site fits below it.  Both metrics' instantiations are set together, so a
-// euclidean call and a cosine call cannot lower each other's attribute either.  (The other caches below are statics of the metric's own
-// template instance of topk_stream / topk_collect: each sets its own kernels only.)
-static int topk_qreg_lds_attr() {
-  static bool done = false;
-  if (done) return SLIC_OK;
-  constexpr int LDS_MAX = 160 * 1024;
-#define TK_ATTR_Q(NK, GS, EU) SLIC_HIP_CHECK(hipFuncSetAttribute((const void*)topk_partial_qreg<NK, GS, EU>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX))
-  TK_ATTR_Q(16, 4, false); TK_ATTR_Q(8, 4, false); TK_ATTR_Q(4, 4, false); TK_ATTR_Q(16, 2, false); TK_ATTR_Q(8, 2, false); TK_ATTR_Q(4, 2, false);
-  TK_ATTR_Q(16, 4, true); TK_ATTR_Q(8, 4, true); TK_ATTR_Q(4, 4, true); TK_ATTR_Q(16, 2, true); TK_ATTR_Q(8, 2, true); TK_ATTR_Q(4, 2, true);
-#undef TK_ATTR_Q
-  done = true;
-  return SLIC_OK;
-}
+// different dynamic-LDS sizes: each asks slic_lds_limit for its own size, and the limit only ever rises.
 
 // EU: per-wave LDS slot of a tile's half norms in the register-operand kernels (tk_bias_init)
 #define TK_EU_LDS(EU) ((EU) ? (size_t)4 * TK_BG * sizeof(float) : (size_t)0)
@@ -1300,40 +1283,31 @@ static int topk_stream(const float* Qn, int Nq, const float* Gn, int Ng, int D, 
   pcap = pcap > TK_PC_MAX ? TK_PC_MAX : pcap;
   SLIC_REQUIRE(pcap >= 2, "slic_cosine_topk: k = %d leaves no LDS for the pending buffers", k);
   const size_t lds = fixed + (size_t)4 * pcap * 64 * 8 + 16;
-  static size_t lds_set = 0;
-  if (lds > lds_set) {
-    SLIC_HIP_CHECK(hipFuncSetAttribute((const void*)topk_partial_kernel<EU>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    lds_set = lds;
-  }
   dim3 grid((unsigned)slic_cdiv(Nq, TK_BQ), (unsigned)S);
   const bool dma_ok = (int64_t)per * D * 4 < (1ll << 31) && (int64_t)TK_BQ * D * 4 < (1ll << 31);
   SLIC_REQUIRE(!qmap || (dma_ok && D <= 512), "slic_cosine_topk: internal: the query map needs the register-operand kernel");
   // LDS-DMA kernel unless a gallery slice exceeds the 32-bit byte range of one buffer resource (> 2 GiB: then the register-staged one)
   if (dma_ok) {
-    static size_t lds_set2 = 0;
-    if (lds > lds_set2) {
-      SLIC_HIP_CHECK(hipFuncSetAttribute((const void*)topk_partial_dma<4, EU>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      SLIC_HIP_CHECK(hipFuncSetAttribute((const void*)topk_partial_dma<2, EU>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      lds_set2 = lds;
-    }
     int* gthr = w.take<int>((size_t)Nq);
     SLIC_HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)gthr, (int)0x807FFFFF, (size_t)Nq, st));   // the image of -inf
 #ifndef TK_NO_QREG
     if (D <= 512) {
-      { const int rc_ = topk_qreg_lds_attr(); if (rc_) return rc_; }
-#define TK_LAUNCH_QREG(NK, GS) topk_partial_qreg<NK, GS, EU><<<grid, dim3(256), lds, st>>>(Qn, Nq, Gn, Ng, D, k, self_mask, per, pcap, pval, pidx, gthr, 1, qmap, nq_dev, ghn)
-      if (pcap >= 12) {                                       // pending columns long enough for groups of four scores
-        if (D > 256) TK_LAUNCH_QREG(16, 4); else if (D > 128) TK_LAUNCH_QREG(8, 4); else TK_LAUNCH_QREG(4, 4);
-      } else {
-        if (D > 256) TK_LAUNCH_QREG(16, 2); else if (D > 128) TK_LAUNCH_QREG(8, 2); else TK_LAUNCH_QREG(4, 2);
-      }
-#undef TK_LAUNCH_QREG
+#define TK_QREG(GS) (D > 256 ? topk_partial_qreg<16, GS, EU> : D > 128 ? topk_partial_qreg<8, GS, EU> : topk_partial_qreg<4, GS, EU>)
+      const auto kern = pcap >= 12 ? TK_QREG(4) : TK_QREG(2);   // 4: pending columns long enough for groups of four scores
+#undef TK_QREG
+      SLIC_LDS_LIMIT(kern, lds);
+      kern<<<grid, dim3(256), lds, st>>>(Qn, Nq, Gn, Ng, D, k, self_mask, per, pcap, pval, pidx, gthr, 1, qmap, nq_dev, ghn);
     } else
 #endif
-    if (pcap >= 12) topk_partial_dma<4, EU><<<grid, dim3(256), lds, st>>>(Qn, Nq, Gn, Ng, D, k, self_mask, per, pcap, pval, pidx, gthr, ghn);
-    else topk_partial_dma<2, EU><<<grid, dim3(256), lds, st>>>(Qn, Nq, Gn, Ng, D, k, self_mask, per, pcap, pval, pidx, gthr, ghn);
-  } else
-  topk_partial_kernel<EU><<<grid, dim3(256), lds, st>>>(Qn, Nq, Gn, Ng, D, k, self_mask, per, (2 * pcap) & ~1, pval, pidx, ghn);
+    {
+      const auto kern = pcap >= 12 ? topk_partial_dma<4, EU> : topk_partial_dma<2, EU>;
+      SLIC_LDS_LIMIT(kern, lds);
+      kern<<<grid, dim3(256), lds, st>>>(Qn, Nq, Gn, Ng, D, k, self_mask, per, pcap, pval, pidx, gthr, ghn);
+    }
+  } else {
+    SLIC_LDS_LIMIT(topk_partial_kernel<EU>, lds);
+    topk_partial_kernel<EU><<<grid, dim3(256), lds, st>>>(Qn, Nq, Gn, Ng, D, k, self_mask, per, (2 * pcap) & ~1, pval, pidx, ghn);
+  }
   SLIC_LAUNCH_CHECK();
   SLIC_REQUIRE((int64_t)S * k <= 64 * TKM_PER, "slic_cosine_topk: slices * k = %d exceeds the merge kernel's %d entries", S * k, 64 * TKM_PER);
   topk_merge_kernel<!EU><<<dim3((unsigned)slic_cdiv(Nq, 4)), dim3(256), 0, st>>>(pval, pidx, S, Nq, k, out_idx, out_dist, qmap, nq_dev);
@@ -1357,12 +1331,11 @@ static int topk_collect(const TopkCollectPlan& c, const float* Qn, int Nq, const
     const int kh = 1 + ((c.ms + 2) / 4) * 4;
     const int pcap = TK_PC_MAX;
     const size_t lds = (size_t)2 * 2 * TK_BQ * TK_BK * sizeof(float) + (size_t)4 * kh * 32 * 8 + (size_t)4 * pcap * 64 * 8 + 16 + TK_EU_LDS(EU);
-    { const int rc_ = topk_qreg_lds_attr(); if (rc_) return rc_; }
     dim3 grid((unsigned)slic_cdiv(Nq, TK_BQ), (unsigned)c.S1);
     const int ns = c.S1 * c.per1;
-#define TK_LAUNCH_S(NK) topk_partial_qreg<NK, 4, EU><<<grid, dim3(256), lds, st>>>(Qn, Nq, Gn, ns, D, c.ms, 0, c.per1, pcap, pval1, pidx1, nullptr, c.gstep, nullptr, nullptr, ghn)
-    if (D > 256) TK_LAUNCH_S(16); else if (D > 128) TK_LAUNCH_S(8); else TK_LAUNCH_S(4);
-#undef TK_LAUNCH_S
+    const auto kern = D > 256 ? topk_partial_qreg<16, 4, EU> : D > 128 ? topk_partial_qreg<8, 4, EU> : topk_partial_qreg<4, 4, EU>;
+    SLIC_LDS_LIMIT(kern, lds);
+    kern<<<grid, dim3(256), lds, st>>>(Qn, Nq, Gn, ns, D, c.ms, 0, c.per1, pcap, pval1, pidx1, nullptr, c.gstep, nullptr, nullptr, ghn);
     SLIC_LAUNCH_CHECK();
     topk_thresholds<<<dim3((unsigned)slic_cdiv(Nq, 4)), dim3(256), 0, st>>>(pval1, c.S1, Nq, c.ms, c.m1, tau, cnt, nfail);
     SLIC_LAUNCH_CHECK();
@@ -1375,25 +1348,18 @@ static int topk_collect(const TopkCollectPlan& c, const float* Qn, int Nq, const
     const int S = (int)slic_cdiv(Ng, per);
     const int pcap = TK_PC_MAX;
     const size_t lds = (size_t)4 * TK_BG * TK_BK * sizeof(float) + (size_t)4 * pcap * 64 * 8 + TK_EU_LDS(EU);
-    static bool attr_set = false;                              // (one per metric: its own instantiations, its own size)
-    if (!attr_set) {
-#define TK_ATTR(NK, GS) SLIC_HIP_CHECK(hipFuncSetAttribute((const void*)topk_collect_qreg<NK, GS, EU>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds))
-      TK_ATTR(16, 4); TK_ATTR(8, 4); TK_ATTR(4, 4);
-      if constexpr (!EU) { TK_ATTR(16, 2); TK_ATTR(8, 2); TK_ATTR(4, 2); TK_ATTR(16, 1); TK_ATTR(8, 1); TK_ATTR(4, 1); }
-#undef TK_ATTR
-      attr_set = true;
-    }
     dim3 grid((unsigned)slic_cdiv(Nq, TK_BQ), (unsigned)S);
     // scores tested per wave-wide branch: with ~0.4 % of the scores passing, SOME lane of the wave passes in most groups of four, so the
     // group maximum of the streaming kernels buys little here; SLIC_TOPK_GS = 1 / 2 / 4 selects (experiments; default below; the euclidean
     // search keeps the default: its GS = 1 instance at 16 k-tiles would spill)
     const char* ge = getenv("SLIC_TOPK_GS");
     const int gs = ge ? atoi(ge) : 4;
-#define TK_LAUNCH_C(NK, GS) topk_collect_qreg<NK, GS, EU><<<grid, dim3(256), lds, st>>>(Qn, Nq, Gn, Ng, D, self_mask, per, pcap, tau, cnt, cand, c.cap, ghn)
-#define TK_LAUNCH_CG(NK) do { if constexpr (EU) TK_LAUNCH_C(NK, 4); else if (gs == 1) TK_LAUNCH_C(NK, 1); else if (gs == 2) TK_LAUNCH_C(NK, 2); else TK_LAUNCH_C(NK, 4); } while (0)
-    if (D > 256) TK_LAUNCH_CG(16); else if (D > 128) TK_LAUNCH_CG(8); else TK_LAUNCH_CG(4);
-#undef TK_LAUNCH_CG
-#undef TK_LAUNCH_C
+#define TK_COLLECT(GS) (D > 256 ? topk_collect_qreg<16, GS, EU> : D > 128 ? topk_collect_qreg<8, GS, EU> : topk_collect_qreg<4, GS, EU>)
+    auto kern = TK_COLLECT(4);
+    if constexpr (!EU) kern = gs == 1 ? TK_COLLECT(1) : gs == 2 ? TK_COLLECT(2) : kern;
+#undef TK_COLLECT
+    SLIC_LDS_LIMIT(kern, lds);
+    kern<<<grid, dim3(256), lds, st>>>(Qn, Nq, Gn, Ng, D, self_mask, per, pcap, tau, cnt, cand, c.cap, ghn);
     SLIC_LAUNCH_CHECK();
   }
   // ---- 3. the k best candidates of every query; 4. whoever fell outside [k, TKC_CAP] through the streaming path (normally nobody)
