@@ -683,6 +683,31 @@ int slic_nce_fused_update(float* bank_l, float* bank_ab, const int64_t* y, const
 int slic_nce_fused_bwd(const float* rows, const float* scores, const float* lse, int B, int K1, int D, float T,
                        const float* gscale, float* df, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Classifier head (coclr_classify.py: nn.CrossEntropyLoss() + calc_topk_accuracy(logit, target, (1, 5)) on the `linear` head of
+ * models/resnet.py:192-201): mean-reduced softmax cross-entropy with general int64 targets, the rank of the target logit from
+ * the same pass, and a dropout whose mask is recomputed from a counter-based generator.
+ * ---------------------------------------------------------------------------------------- */
+/* logits: [B, C] fp32 with row stride ld >= C (elements); targets: [B] int64.
+ *   lse      [B][2]  (row maximum, log of the sum of exp(x - maximum)) — the log-sum-exp in two parts, kept for the backward
+ *   rowloss  [B]     log-sum-exp - x[target]
+ *   loss     [1]     mean of rowloss (NaN when a target is out of range)
+ *   topk_hits int32 [SLIC_CE_HITS_HEAD + B] = {rows whose target is outside [0, C), top-1 hits, top-5 hits, rank[0 .. B)};
+ *            rank[b] = #{j : x[b][j] > x[b][t]} + #{j < t : x[b][j] == x[b][t]} (torch.topk's order on distinct values, lower
+ *            index first on ties), -1 for a row whose target is out of range — such a row reads no x[b][t] and adds nothing to
+ *            the hits; the caller checks topk_hits[0] (an argument error it reports after the launch). */
+#define SLIC_CE_HITS_HEAD 3
+int slic_softmax_ce_fwd(const float* logits, int64_t ld, int B, int C, const int64_t* targets, float* lse, float* rowloss,
+                        float* loss, int32_t* topk_hits, void* stream);
+/* dlogits [B, C] dense = (softmax - onehot(target)) * (*gscale, NULL = 1) / B */
+int slic_softmax_ce_bwd(const float* logits, int64_t ld, const float* lse, const int64_t* targets, int B, int C,
+                        const float* gscale, float* dlogits, void* stream);
+/* y[i] = keep(i) ? x[i] / (1 - p) : 0, keep(i) drawn with probability 1 - p from Philox4x32-10 keyed by seed at counter
+ * (i / 4, offset): the mask is a function of (seed, offset, i) and is recomputed by the backward, which applies the same map to
+ * dy.  p = 1 gives zeros, p = 0 a copy.  This is not torch's dropout stream: the same seed gives a different (equally valid) mask. */
+int slic_dropout_fwd(const float* x, int64_t n, float p, uint64_t seed, uint64_t offset, float* y, void* stream);
+int slic_dropout_bwd(const float* dy, int64_t n, float p, uint64_t seed, uint64_t offset, float* dx, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -154,6 +154,11 @@ SIGNATURES = {
     "slic_nce_fused_bwd": (I, [P, P, P, I, I, I, F, P, P, P]),
     "slic_softmax_ce0_fwd": (I, [P, I, I, P, P, P, P]),
     "slic_softmax_ce0_bwd": (I, [P, P, I, I, P, P, P]),
+    # classifier head
+    "slic_softmax_ce_fwd": (I, [P, L, I, I, P, P, P, P, P, P]),
+    "slic_softmax_ce_bwd": (I, [P, L, P, P, I, I, P, P, P]),
+    "slic_dropout_fwd": (I, [P, L, F, ctypes.c_uint64, ctypes.c_uint64, P, P]),
+    "slic_dropout_bwd": (I, [P, L, F, ctypes.c_uint64, ctypes.c_uint64, P, P]),
 }
 
 

@@ -93,6 +93,7 @@ class _NetView:
         self.layer1, self.layer2, self.layer3, self.layer4 = (_LayerView(l) for l in (net.conv2, net.conv3, net.conv4, net.conv5))
         self.no_max_pool = True
         self.projection_head = False
+        self.classifier = False
 
 
 class R3DNet(nn.Module):

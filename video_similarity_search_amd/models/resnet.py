@@ -25,9 +25,11 @@ from functools import partial
 from .. import _lib
 from .._lib import call, ptr, stream
 from .conv_plan import ConvPlan
+from .dropout import apply_mask, next_seed_offset
 
 BN_EPS = 1e-5
 BN_MOMENTUM = 0.1
+CLASSIFIER_FEATURES = 512      # the reference's classifier head is nn.Linear(512, num_classes) whatever the encoder (models/resnet.py:198-200)
 
 
 def conv3x3x3(in_planes, out_planes, stride=1):
@@ -100,7 +102,7 @@ class _Bn:
         self.frozen = False
 
 
-COUNTS = {"bn_bwd": 0, "bn_bwd_fused": 0}     # launches by flavour (diagnostics / tests)
+COUNTS = {"bn_bwd": 0, "bn_bwd_fused": 0, "probe_pass": 0, "segments_saved": 0}     # launches / passes by flavour (diagnostics / tests)
 
 
 _GRAD_VIEWS = [None]       # the pass's {parameter: DistributedDataParallel bucket view} (misc.distributed_helper.data_parallel), or None
@@ -177,6 +179,93 @@ class _Engine:
         if net.projection_head:
             self.fc1 = ConvPlan(net.fc1.in_features, net.fc1.out_features, (1, 1, 1), (1, 1, 1), (0, 0, 0), (1, 1, 1), device)
             self.fc2 = ConvPlan(net.fc2.in_features, net.fc2.out_features, (1, 1, 1), (1, 1, 1), (0, 0, 0), (1, 1, 1), device)
+        if net.classifier:
+            # `linear` as a 1x1x1 GEMM plan like fc1 / fc2.  The plan wants output channels in fours and num_classes is anything
+            # (101, 51, 400): weight and bias are copied into zero-padded operands, the logits come back as the [B, num_classes]
+            # view (row stride n_pad) of the padded product, and the padded columns of the gradient are zero
+            lin = self.linear_mod
+            self.n_cls = lin.out_features
+            self.n_pad = (self.n_cls + 3) // 4 * 4
+            self.lin = ConvPlan(lin.in_features, self.n_pad, (1, 1, 1), (1, 1, 1), (0, 0, 0), (1, 1, 1), device)
+            self._lin_w = self._lin_b = None
+
+    # ------------------------------------------------------------------ classifier head
+    @property
+    def linear_mod(self):
+        lin = self.net.linear
+        return lin[1] if isinstance(lin, nn.Sequential) else lin
+
+    @property
+    def dropout_mod(self):
+        lin = self.net.linear
+        return lin[0] if isinstance(lin, nn.Sequential) else None
+
+    def _lin_operands(self):
+        """(weight [n_pad, 512], bias [n_pad]) of this pass: the parameters themselves when num_classes is a multiple of four"""
+        lin = self.linear_mod
+        if self.n_pad == self.n_cls:
+            return lin.weight, lin.bias
+        if self._lin_w is None:
+            self._lin_w = torch.zeros(self.n_pad, lin.in_features, dtype=torch.float32, device=self.device)
+            self._lin_b = torch.zeros(self.n_pad, dtype=torch.float32, device=self.device)
+        with torch.no_grad():
+            self._lin_w[:self.n_cls].copy_(lin.weight)
+            self._lin_b[:self.n_cls].copy_(lin.bias)
+        return self._lin_w, self._lin_b
+
+    def _classify(self, pooled, training, ctx):
+        """pooled [B, 512] -> dropout (the Dropout child's own training flag, as in the reference) -> linear; ctx (or None) gets
+        what the backward needs"""
+        net = self.net
+        B = pooled.shape[0]
+        if net.projection_head and training:
+            # the reference still runs fc1 -> bn_proj -> relu -> fc2 and drops the result (models/resnet.py:294-307): all anybody can
+            # observe is bn_proj's running statistics and counter moving, so fc1 + the statistics are run and the rest is not
+            h1, part = self.fc1.forward(pooled.view(B, 1, 1, 1, self.feat), self.fc1.pack_fwd(net.fc1.weight), B, bias=net.fc1.bias,
+                                        want_stats=True)
+            self._bn_train(_Bn(net.bn_proj), part, B)
+        xin = pooled
+        drop = self.dropout_mod
+        if drop is not None and drop.training and drop.p > 0.0:
+            key = (float(drop.p),) + next_seed_offset(pooled.device, pooled.numel())
+            xin = apply_mask(pooled, *key)
+            if ctx is not None:
+                ctx["drop"] = key
+        w, b = self._lin_operands()
+        self.lin.drop_packs()
+        y, _ = self.lin.forward(xin.view(B, 1, 1, 1, self.feat), self.lin.pack_fwd(w), B, bias=b)
+        if ctx is not None:
+            ctx.update(xin=xin, lin_w=w)
+        y = y.view(B, self.n_pad)
+        return y if self.n_pad == self.n_cls else y[:, :self.n_cls]
+
+    def _classify_bwd(self, ctx, dy, need_dx, new_like):
+        """returns (gradient wrt the pooled features or None, {parameter: gradient})"""
+        lin = self.linear_mod
+        B = dy.shape[0]
+        if self.n_pad != self.n_cls:
+            dpad = torch.zeros(B, self.n_pad, dtype=torch.float32, device=dy.device)
+            dpad[:, :self.n_cls].copy_(dy)
+            dy = dpad
+        d5 = dy.view(B, 1, 1, 1, self.n_pad)
+        gw, gb = new_like(lin.weight), new_like(lin.bias)
+        if self.n_pad == self.n_cls:
+            self.lin.wgrad(ctx["xin"].view(B, 1, 1, 1, self.feat), d5, B, gw)
+            call("slic_colsum", ptr(dy), B, self.n_pad, ptr(gb), stream())
+        else:
+            gwp = torch.empty(self.n_pad, lin.in_features, dtype=torch.float32, device=dy.device)
+            gbp = torch.empty(self.n_pad, dtype=torch.float32, device=dy.device)
+            self.lin.wgrad(ctx["xin"].view(B, 1, 1, 1, self.feat), d5, B, gwp)
+            call("slic_colsum", ptr(dy), B, self.n_pad, ptr(gbp), stream())
+            gw.copy_(gwp[:self.n_cls])
+            gb.copy_(gbp[:self.n_cls])
+        grads = {lin.weight: gw, lin.bias: gb}
+        if not need_dx:
+            return None, grads
+        dpool = self.lin.dgrad(d5, self.lin.pack_dgrad(ctx["lin_w"]), B).view(B, self.feat)
+        if "drop" in ctx:
+            dpool = apply_mask(dpool, *ctx["drop"], backward=True)
+        return dpool, grads
 
     # ------------------------------------------------------------------ small helpers
     def _side_stream(self):
@@ -339,7 +428,9 @@ class _Engine:
         elif si <= 4:
             mods = [getattr(net, f"layer{si}")]
         else:
-            mods = [net.fc1, net.bn_proj, net.fc2] if net.projection_head else []
+            # classifier: the projection head's output is dropped (models/resnet.py:305-307), so fc1 / bn_proj / fc2 are outside the
+            # graph and keep grad None
+            mods = [net.linear] if net.classifier else [net.fc1, net.bn_proj, net.fc2] if net.projection_head else []
         return [p for m in mods for p in m.parameters() if p.requires_grad]
 
     def _conv_bn_act(self, plan, inp, weight, bnmod, res, relu, training, B, keep=False):
@@ -439,13 +530,15 @@ class _Engine:
                         saved.append(dict(x=xin, z1=z1, a1=a1, b1=b1, z2=z2, out=out, b2=b2, zd=zd, bd=bd, zl=z2, bl=b2))
                 a = out
             return a, (dict(blocks=saved) if save else None)
-        # head: pool -> fc2(relu(bn_proj(fc1(x))))   (models/resnet.py:286-299)
+        # head: pool -> fc2(relu(bn_proj(fc1(x))))   (models/resnet.py:286-299), or pool -> dropout -> linear with classifier=True (:305-307)
         a = inp
         To, Ho, Wo = self.final_dims
         S = To * Ho * Wo
         pooled = torch.empty(B, self.feat, dtype=torch.float32, device=dev)
         call("slic_avgpool_fwd", ptr(a), B, S, self.feat, ptr(pooled), stream())
         ctx = dict(last_shape=tuple(a.shape), pooled=pooled) if save else None
+        if net.classifier:
+            return self._classify(pooled, training, ctx), ctx
         if not net.projection_head:
             return pooled, ctx
         bnp = _Bn(net.bn_proj)
@@ -522,7 +615,12 @@ class _Engine:
 
         if si == 5:
             dy = dout
-            if net.projection_head:
+            need_dx = ctx.get("need_dx", True)
+            if net.classifier:
+                dpool, grads = self._classify_bwd(ctx, dy, need_dx, new_like)
+                if not need_dx:                    # linear probe: nothing below the head is in the graph
+                    return None, grads
+            elif net.projection_head:
                 ah, h1, bnp, pooled = ctx["ah"], ctx["h1"], ctx["bnp"], ctx["pooled"]
                 d5 = dy.view(B, 1, 1, 1, -1)
                 grads[net.fc2.weight] = self.fc2.wgrad(ah.view(B, 1, 1, 1, -1), d5, B, new_like(net.fc2.weight))
@@ -696,12 +794,15 @@ class _SegmentFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, inp, engine, si, training, *params):
         out, saved = engine.seg_forward(si, inp, training=training, save=True)
+        COUNTS["segments_saved"] += 1
         # the saved context must not hold the output OBJECT (output -> grad_fn -> ctx -> output would be a reference
         # cycle that pins HBM until Python's cycle collector runs): keep a detached alias of the same storage
         if si == 0 and engine.pool_in is None:
             saved["a0"] = out.detach()
         elif 1 <= si <= 4:
             saved["blocks"][-1]["out"] = out.detach()
+        if si == engine.N_SEG - 1:
+            saved["need_dx"] = bool(inp.requires_grad)
         ctx.engine, ctx.si, ctx.saved, ctx.params = engine, si, saved, params
         if si == 0:
             engine._pass_id += 1
@@ -735,10 +836,16 @@ class ResNet(nn.Module):
                  predict_temporal_ds=False, spatio_temporal_attention=False, projection_head=True,
                  num_classes=101, classifier=False, dropout=None):
         super().__init__()
-        if spatio_temporal_attention or predict_temporal_ds or classifier:
-            raise NotImplementedError("attention / temporal-ds / classifier heads are off in every SLIC config "
+        if spatio_temporal_attention or predict_temporal_ds:
+            raise NotImplementedError("attention / temporal-ds heads are off in every SLIC config "
                                       "(config/default_params.py:97) and outside the hot path")
         block_inplanes = [int(x * widen_factor) for x in block_inplanes]
+        if classifier and block_inplanes[3] * block.expansion != CLASSIFIER_FEATURES:
+            # the reference hard-codes nn.Linear(512, num_classes) behind x.view(-1, 512) (models/resnet.py:198-200, 306): at any other
+            # pooled width it folds batch rows into features (or fails) without a word
+            raise ValueError(f"classifier=True needs a pooled width of {CLASSIFIER_FEATURES} (BasicBlock depths at widen_factor 1): this "
+                             f"model pools to {block_inplanes[3] * block.expansion} features, which the reference's hard-coded "
+                             f"x.view(-1, {CLASSIFIER_FEATURES}) would silently mis-shape")
         self.in_planes = block_inplanes[0]
         self.no_max_pool = no_max_pool
         self.conv1 = nn.Conv3d(n_input_channels, self.in_planes, kernel_size=(conv1_t_size, 7, 7),
@@ -762,6 +869,18 @@ class ResNet(nn.Module):
             self.fc1 = nn.Linear(block_inplanes[3] * block.expansion, hidden_layer)
             self.bn_proj = nn.BatchNorm1d(hidden_layer)
             self.fc2 = nn.Linear(hidden_layer, out_dim)
+        if classifier:
+            print('==> setting up linear layer for classification')
+            if dropout is not None and dropout > 0.0:
+                print('==> setting up Dropout layer')
+                self.linear = nn.Sequential(nn.Dropout(dropout), nn.Linear(CLASSIFIER_FEATURES, num_classes))
+            else:
+                self.linear = nn.Linear(CLASSIFIER_FEATURES, num_classes)
+            for name, param in self.linear.named_parameters():         # _initialize_weights (models/resnet.py:247-252)
+                if 'bias' in name:
+                    nn.init.constant_(param, 0.0)
+                elif 'weight' in name:
+                    nn.init.normal_(param, mean=0.0, std=0.01)
         for m in self.modules():
             if isinstance(m, nn.Conv3d):
                 nn.init.kaiming_normal_(m.weight, mode='fan_out', nonlinearity='relu')
@@ -821,12 +940,31 @@ def _flush_engine_counters(module, prefix, keep_vars):
             flush()
 
 
+def _is_linear_probe(module, params):
+    """the linear-probe state: eval mode and no trainable parameter outside `linear` (SLIC_PROBE=0 keeps such a model on the six
+    autograd segments, for measurements)"""
+    if not getattr(module, "classifier", False) or module.training or os.environ.get("SLIC_PROBE", "1") == "0":
+        return False
+    own = {id(p) for p in module.linear.parameters()}
+    return all(id(p) in own for p in params)
+
+
 def run_engine(eng, module, x):
     """drive one encoder through its engine: autograd segments whenever a backward may follow — train mode (batch statistics)
     or eval mode (BatchNorm frozen on its running statistics: the reference's ResNet.forward is an ordinary autograd graph in
     any mode, models/resnet.py:255-312) — a plain inference pass with BatchNorm folded into the conv epilogues otherwise"""
     params = [p for p in module.parameters() if p.requires_grad]
     eng.grad_views = getattr(module, "_slic_grad_views", None)
+    if torch.is_grad_enabled() and params and _is_linear_probe(module, params) and not x.requires_grad:
+        # coclr_classify.py --train_what last: everything but `linear` frozen, model.eval().  The encoder below the head is the
+        # plain inference pass (BatchNorm folded into the conv epilogues, nothing saved, no autograd node); the head alone is a node
+        COUNTS["probe_pass"] += 1
+        with torch.no_grad():
+            a = x
+            eng.prepack(with_dgrad=False)
+            for si in range(eng.N_SEG - 1):
+                a, _ = eng.seg_forward(si, a, False, False)
+        return _SegmentFn.apply(a, eng, eng.N_SEG - 1, False, *eng.seg_params(eng.N_SEG - 1))
     if torch.is_grad_enabled() and params:
         a = x
         eng.prepack(with_dgrad=True)
