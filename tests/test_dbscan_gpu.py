@@ -51,6 +51,7 @@ def test_goldens_exact(gpu, case):
 @pytest.mark.parametrize("N,D,eps,ms", [
     (3000, 8, 0.05, 2), (20000, 8, 0.05, 3), (5000, 100, 0.14, 5), (8000, 128, 0.14, 2), (6000, 128, 0.3, 3),
     (4000, 512, 0.14, 3), (3000, 512, 0.3, 5), (12000, 100, 0.3, 2),
+    (3000, 200, 0.3, 3), (3000, 320, 0.3, 3),                        # db_tiles<NK = 8> and <NK = 12>
 ])
 def test_matches_fp64_oracle(gpu, N, D, eps, ms):
     X = _blobs(N + D, N, D, K=max(4, N // 400), spread=0.15 if eps < 0.1 else 0.3)

@@ -21,14 +21,13 @@
 //   number  pointer jumping to the roots, a prefix scan over the root flags gives every root its cluster number.
 //   border  Xb x Xc (full rectangle): a hit takes atomicMin of the core's root; the smallest root is the smallest cluster number.
 // Every decision is an integer fixed by the float64 rule, so labels, core flags and counts are the same on every run.
-#include "common.h"
+#include "mfma_ring.h"
 #include <math.h>
 #include <limits.h>
 #include <stdlib.h>
 #include <algorithm>
 
 #define DB_B 128              // rows per tile (both operands)
-#define DB_BK 32              // k columns per ring stage
 #define DB_PC 32              // band pairs pending per lane
 #define DB_SLICE 16           // gallery tiles per workgroup
 #define DB_SCAN_T 1024        // threads of the one-workgroup scans
@@ -36,10 +35,6 @@
 #define DB_SURE 0x40000000     // pending entry of the link pass that is a neighbour already (row indices < 2^30)
 
 enum { DB_COUNT = 0, DB_LINK = 1, DB_BORDER = 2 };
-
-__device__ __forceinline__ int db_off(int row, int chunk) {
-  return row * DB_BK + ((chunk ^ ((row >> 1) & 7)) << 2);
-}
 
 __device__ __forceinline__ int db_ld(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void db_st(int* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -115,7 +110,7 @@ template <int NK, int MODE>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void db_tiles(DbArgs p) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   static_assert(NK % 4 == 0, "a gallery tile is a whole number of ring turns");
-  constexpr int STAGE_FLOATS = DB_B * DB_BK;
+  constexpr int STAGE_FLOATS = DB_B * SLIC_RT_BK;
   constexpr bool TRI = MODE != DB_BORDER;
   int* pend = (int*)(lds + 4 * STAGE_FLOATS);                  // [4 waves][DB_PC][64] gallery rows, one column per lane
   int* groot = pend + 4 * DB_PC * 64;                          // [128] cached roots of the gallery tile
@@ -190,12 +185,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   const int klim = Dp - cq * 4;
   auto issue = [&](int tile, int kt, int stage) {
     float* Gs = lds + stage * STAGE_FLOATS;
-    const bool kin = kt * DB_BK < klim && tile < ntl;
-    const unsigned kb = (unsigned)kt * (DB_BK * 4u);
+    const bool kin = kt * SLIC_RT_BK < klim && tile < ntl;
+    const unsigned kb = (unsigned)kt * (SLIC_RT_BK * 4u);
     const unsigned gb = tile < ntl ? (unsigned)tl[tile] * (unsigned)(DB_B * Dp * 4) : 0u;
 #pragma unroll
     for (int i = 0; i < 4; ++i)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_g, (__attribute__((address_space(3))) void*)(Gs + (8 * wave + 32 * i) * DB_BK),
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_g, (__attribute__((address_space(3))) void*)(Gs + (8 * wave + 32 * i) * SLIC_RT_BK),
                                                16, (int)(kin ? gb + goff[i] + kb : OOB), 0, 0, 0);
   };
 
@@ -238,7 +233,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   asm volatile("s_waitcnt vmcnt(8)" ::: "memory");             // step 0 has landed
   __builtin_amdgcn_s_barrier();
 #pragma unroll
-  for (int ct = 0; ct < 4; ++ct) a[0][ct] = *(const f32x4*)&lds[db_off(32 * ct + r, h)];
+  for (int ct = 0; ct < 4; ++ct) a[0][ct] = *(const f32x4*)&lds[slic_rt_off(32 * ct + r, h)];
   for (int tile = 0; tile < ntl; ++tile) {
     const int J = tl[tile];
     const int g0 = J * DB_B;
@@ -273,8 +268,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         const int cur = qd & 1, nxt = cur ^ 1;
 #pragma unroll
         for (int ct = 0; ct < 4; ++ct)
-          a[nxt][ct] = qd < 3 ? *(const f32x4*)&Gs[db_off(32 * ct + r, 2 * (qd + 1) + h)]
-                              : *(const f32x4*)&Gn[db_off(32 * ct + r, h)];       // first fragments of the next step
+          a[nxt][ct] = qd < 3 ? *(const f32x4*)&Gs[slic_rt_off(32 * ct + r, 2 * (qd + 1) + h)]
+                              : *(const f32x4*)&Gn[slic_rt_off(32 * ct + r, h)];       // first fragments of the next step
 #pragma unroll
         for (int t = 0; t < 4; ++t)
 #pragma unroll
@@ -570,7 +565,7 @@ extern "C" int slic_dbscan_cosine(const float* X, int64_t N, int ldx, int D, dou
   a.parent = L.parent; a.best = L.best; a.stats = L.stats;
   const int T = (n + DB_B - 1) / DB_B;
   const dim3 grid(T, (T + DB_SLICE - 1) / DB_SLICE);
-  constexpr size_t LDS = (4 * DB_B * DB_BK) * 4 + 4 * DB_PC * 64 * 4 + (DB_B + DB_SLICE + 4) * 4;
+  constexpr size_t LDS = (4 * DB_B * SLIC_RT_BK) * 4 + 4 * DB_PC * 64 * 4 + (DB_B + DB_SLICE + 4) * 4;
 
   a.Xcb = L.Xn;
   { int r = db_launch_tiles<DB_COUNT>(NK, grid, LDS, st, a); if (r) return r; }

@@ -10,21 +10,14 @@
 // (b) the LDS image hands the MFMA its k's in ascending order.  Both hold below.
 //
 // Build: -ffp-contract=off (nothing fuses except explicit fmaf/MFMA).
-#include "common.h"
+#include "mfma_ring.h"
 #include <type_traits>
 #include <math.h>
 #include <stdlib.h>
 
 #define KM_BP 128  // points per workgroup (4 waves x 32)
 #define KM_BC 128  // centroids per workgroup (4 MFMA row tiles per wave)
-#define KM_BK 32   // k per LDS tile
-
-// LDS tile = [128 rows][32 floats]; 16-byte chunk c of row r lives at chunk c ^ ((r>>1)&7):
-// the 16 lanes of a ds_read_b128 group (rows distinct mod 16, same chunk) hit 16 different
-// 16-byte slots of the 256-byte bank row.
-__device__ __forceinline__ int km_off(int row, int chunk) {
-  return row * KM_BK + ((chunk ^ ((row >> 1) & 7)) << 2);
-}
+// LDS tile = [128 rows][32 floats], swizzled: slic_rt_off (mfma_ring.h)
 
 // One workgroup: 128 points x 128 centroids, full D.  Wave w owns points [32w, 32w+32).
 // MFMA roles: A = centroid tile (rows i), B = point tile (cols j)  =>  each lane holds ONE point
@@ -35,8 +28,8 @@ __global__ __launch_bounds__(256) void km_assign_partial(
     int ldc, const float* __restrict__ cnorm, float* __restrict__ pscore,
     int32_t* __restrict__ pidx) {
   constexpr int BC = NCT * 32;
-  __shared__ __attribute__((aligned(16))) float ldsX[2][KM_BP * KM_BK];
-  __shared__ __attribute__((aligned(16))) float ldsC[2][BC * KM_BK];
+  __shared__ __attribute__((aligned(16))) float ldsX[2][KM_BP * SLIC_RT_BK];
+  __shared__ __attribute__((aligned(16))) float ldsC[2][BC * SLIC_RT_BK];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int64_t pblock = (int64_t)blockIdx.x * KM_BP;
   const int cblock = blockIdx.y * BC;
@@ -60,7 +53,7 @@ __global__ __launch_bounds__(256) void km_assign_partial(
   f32x4 gxs[2][2][2], gcs[2][2][2];
   const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
   auto gload = [&](int kt, f32x4 (&gx)[2][2], f32x4 (&gc)[2][2]) {
-    const int k0 = kt * KM_BK;
+    const int k0 = kt * SLIC_RT_BK;
     const bool kin = (k0 + scp * 8) < D;  // D % 8 == 0: a pair of chunks is all in or all out
 #pragma unroll
     for (int p = 0; p < 2; ++p) {
@@ -86,13 +79,13 @@ __global__ __launch_bounds__(256) void km_assign_partial(
       const int row = srow + 64 * p;
       f32x4 e = {gx[p][0].x, gx[p][0].z, gx[p][1].x, gx[p][1].z};
       f32x4 o = {gx[p][0].y, gx[p][0].w, gx[p][1].y, gx[p][1].w};
-      *(f32x4*)&ldsX[buf][km_off(row, 2 * scp)] = e;
-      *(f32x4*)&ldsX[buf][km_off(row, 2 * scp + 1)] = o;
+      *(f32x4*)&ldsX[buf][slic_rt_off(row, 2 * scp)] = e;
+      *(f32x4*)&ldsX[buf][slic_rt_off(row, 2 * scp + 1)] = o;
       if (row < BC) {
         f32x4 ce = {gc[p][0].x, gc[p][0].z, gc[p][1].x, gc[p][1].z};
         f32x4 co = {gc[p][0].y, gc[p][0].w, gc[p][1].y, gc[p][1].w};
-        *(f32x4*)&ldsC[buf][km_off(row, 2 * scp)] = ce;
-        *(f32x4*)&ldsC[buf][km_off(row, 2 * scp + 1)] = co;
+        *(f32x4*)&ldsC[buf][slic_rt_off(row, 2 * scp)] = ce;
+        *(f32x4*)&ldsC[buf][slic_rt_off(row, 2 * scp + 1)] = co;
       }
     }
   };
@@ -104,21 +97,21 @@ __global__ __launch_bounds__(256) void km_assign_partial(
     for (int r = 0; r < 16; ++r) acc[ct][r] = 0.f;
 
   const int r = lane & 31, h = lane >> 5;
-  const int nk = (D + KM_BK - 1) / KM_BK;
+  const int nk = (D + SLIC_RT_BK - 1) / SLIC_RT_BK;
   auto compute = [&](int buf) {
     const float* Cs = ldsC[buf];
     const float* Xs = ldsX[buf];
     f32x4 b[2], a[2][NCT];               // LDS operands of group q+1 are read under group q's MFMAs
-    b[0] = *(const f32x4*)&Xs[km_off(32 * wave + r, h)];
+    b[0] = *(const f32x4*)&Xs[slic_rt_off(32 * wave + r, h)];
 #pragma unroll
-    for (int ct = 0; ct < NCT; ++ct) a[0][ct] = *(const f32x4*)&Cs[km_off(32 * ct + r, h)];
+    for (int ct = 0; ct < NCT; ++ct) a[0][ct] = *(const f32x4*)&Cs[slic_rt_off(32 * ct + r, h)];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const int cur = q & 1, nxt = cur ^ 1;
       if (q < 3) {
-        b[nxt] = *(const f32x4*)&Xs[km_off(32 * wave + r, 2 * (q + 1) + h)];
+        b[nxt] = *(const f32x4*)&Xs[slic_rt_off(32 * wave + r, 2 * (q + 1) + h)];
 #pragma unroll
-        for (int ct = 0; ct < NCT; ++ct) a[nxt][ct] = *(const f32x4*)&Cs[km_off(32 * ct + r, 2 * (q + 1) + h)];
+        for (int ct = 0; ct < NCT; ++ct) a[nxt][ct] = *(const f32x4*)&Cs[slic_rt_off(32 * ct + r, 2 * (q + 1) + h)];
       }
       // k order inside every accumulator: q ascending, t ascending, lane half 0 then 1 => k = 8q + 2t + h ascending
 #pragma unroll
@@ -196,14 +189,13 @@ __global__ __launch_bounds__(256) void km_assign_dma(
   constexpr int BC = NCT * 32;
   constexpr int TC = NCT / WC;                               // centroid tiles per wave
   constexpr int AL = BP / 32;
-  constexpr int STAGE_FLOATS = (BP + BC) * KM_BK;
+  constexpr int STAGE_FLOATS = (BP + BC) * SLIC_RT_BK;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wp = wave % WP, wc = wave / WP;
   const int64_t pblock = (int64_t)blockIdx.x * BP;
   const int cblock = blockIdx.y * BC;
-  const int srow = tid >> 3;
-  const int cq = (tid & 7) ^ ((srow >> 1) & 7);              // SOURCE chunk of this lane (LDS slot = tid & 7)
+  const SlicRtLane ln = slic_rt_lane(tid, D);
   // block-local buffer resources: offsets stay 32-bit whatever N is
   const int64_t xrows = (N - pblock) < BP ? (N - pblock) : BP;
   const int crows = (K - cblock) < BC ? (K - cblock) : BC;
@@ -211,27 +203,15 @@ __global__ __launch_bounds__(256) void km_assign_dma(
       (void*)(Xp + pblock * (int64_t)ldx), 0, (int)(((xrows - 1) * (int64_t)ldx + D) * 4), 0x00020000);
   const __amdgpu_buffer_rsrc_t rs_c = __builtin_amdgcn_make_buffer_rsrc(
       (void*)(Cp + (int64_t)cblock * ldc), 0, (int)((((int64_t)crows - 1) * ldc + D) * 4), 0x00020000);
-  constexpr unsigned OOB = 0xFFFFFF00u;
   unsigned xoff[AL], coff[NCT];
-#pragma unroll
-  for (int i = 0; i < AL; ++i) xoff[i] = (srow + 32 * i) < xrows ? ((unsigned)(srow + 32 * i) * (unsigned)ldx + cq * 4) * 4u : OOB;
-#pragma unroll
-  for (int i = 0; i < NCT; ++i) coff[i] = (srow + 32 * i) < crows ? ((unsigned)(srow + 32 * i) * (unsigned)ldc + cq * 4) * 4u : OOB;
-  const int klim = D - cq * 4;                                // this lane's chunk of k-tile kt is inside D iff 32 kt < klim
-  const int nk = (D + KM_BK - 1) / KM_BK;
+  slic_rt_offsets(xoff, ln, (unsigned)ldx * 4u, xrows);
+  slic_rt_offsets(coff, ln, (unsigned)ldc * 4u, crows);
+  const int nk = (D + SLIC_RT_BK - 1) / SLIC_RT_BK;
   auto issue = [&](int kt, int stage) {
     float* Xs = km_lds + stage * STAGE_FLOATS;
-    float* Cs = Xs + BP * KM_BK;
-    const bool kin = kt * KM_BK < klim;                       // false for every lane once kt >= nk: all-OOB (zero) DMAs
-    const unsigned kb = (unsigned)kt * (KM_BK * 4u);
-#pragma unroll
-    for (int i = 0; i < AL; ++i)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_x, (__attribute__((address_space(3))) void*)(Xs + (8 * wave + 32 * i) * KM_BK),
-                                               16, (int)((kin && xoff[i] != OOB) ? xoff[i] + kb : OOB), 0, 0, 0);
-#pragma unroll
-    for (int i = 0; i < NCT; ++i)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_c, (__attribute__((address_space(3))) void*)(Cs + (8 * wave + 32 * i) * KM_BK),
-                                               16, (int)((kin && coff[i] != OOB) ? coff[i] + kb : OOB), 0, 0, 0);
+    const bool kin = ln.kin(kt);                               // false for every lane once kt >= nk: all-OOB (zero) DMAs
+    slic_rt_issue<true>(rs_x, Xs, wave, xoff, 0u, kt, kin);
+    slic_rt_issue<true>(rs_c, Xs + BP * SLIC_RT_BK, wave, coff, 0u, kt, kin);
   };
   f32x16 acc[TC];
 #pragma unroll
@@ -241,30 +221,7 @@ __global__ __launch_bounds__(256) void km_assign_dma(
   const int r = lane & 31, h = lane >> 5;
   auto compute = [&](int stage) {
     const float* Xs = km_lds + stage * STAGE_FLOATS;
-    const float* Cs = Xs + BP * KM_BK;
-    f32x4 b[2], a[2][TC];
-    b[0] = *(const f32x4*)&Xs[km_off(32 * wp + r, h)];
-#pragma unroll
-    for (int ct = 0; ct < TC; ++ct) a[0][ct] = *(const f32x4*)&Cs[km_off(32 * (wc * TC + ct) + r, h)];
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int cur = q & 1, nxt = cur ^ 1;
-      if (q < 3) {
-        b[nxt] = *(const f32x4*)&Xs[km_off(32 * wp + r, 2 * (q + 1) + h)];
-#pragma unroll
-        for (int ct = 0; ct < TC; ++ct) a[nxt][ct] = *(const f32x4*)&Cs[km_off(32 * (wc * TC + ct) + r, 2 * (q + 1) + h)];
-      }
-      // k order inside every accumulator: q ascending, t ascending, lane half 0 then 1 => k = 8q + 2t + h ascending
-#pragma unroll
-      for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int ct = 0; ct < TC; ++ct)
-          acc[ct] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[cur][ct][t], b[cur][t], acc[ct], 0, 0, 0);
-      if (q < 3) __builtin_amdgcn_sched_group_barrier(0x100, 1 + TC, 0);
-      __builtin_amdgcn_sched_group_barrier(0x008, 4 * TC, 0);
-    }
-    __builtin_amdgcn_s_setprio(0);
+    slic_rt_compute_stage<TC>(acc, Xs, Xs + BP * SLIC_RT_BK, 32 * wc * TC, 32 * wp, r, h);
   };
   constexpr int PER_STAGE = AL + NCT;
 #pragma unroll
@@ -273,13 +230,13 @@ __global__ __launch_bounds__(256) void km_assign_dma(
   for (int s0 = 0; s0 < nk; s0 += STAGES) {
 #pragma unroll
     for (int sidx = 0; sidx < STAGES; ++sidx) {
-      asm volatile("s_waitcnt vmcnt(%0)" ::"n"((STAGES - 2) * PER_STAGE) : "memory");
+      slic_rt_wait<(STAGES - 2) * PER_STAGE>();
       __builtin_amdgcn_s_barrier();
       issue(s0 + sidx + STAGES - 1, (sidx + STAGES - 1) % STAGES);
       compute(sidx);
     }
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  slic_rt_wait<0>();
   // the lane's centroid index rises with (ct, g), so a strict '<' alone keeps the first minimum; cn - 2 acc as ONE fma is the
   // same float as the rounded difference (2 acc is exact)
   float best = INFINITY;
@@ -343,7 +300,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   }
   static_assert(NK % ST == 0 && ST == 4, "a point tile is a whole number of ring turns; the DMA's LDS base (M0) reaches 64 KB: 4 stages of 16 KB");
   constexpr int BP = 128;
-  constexpr int STAGE_FLOATS = BP * KM_BK;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r = lane & 31, h = lane >> 5;
@@ -367,15 +323,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   f32x4 cr[NK][4];
   {
     const int crow = cbase + r;
-    const float* cp = Cp + (int64_t)(crow < K ? crow : K - 1) * ldc;
-#pragma unroll
-    for (int kt = 0; kt < NK; ++kt)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int c = 32 * kt + 8 * q + 4 * h;
-        f32x4 z = {0.f, 0.f, 0.f, 0.f};
-        cr[kt][q] = (c < D && crow < K) ? *(const f32x4*)(cp + c) : z;
-      }
+    slic_rt_load_frags(cr, Cp + (int64_t)(crow < K ? crow : K - 1) * ldc, D, h, crow < K);
   }
   // accumulator element g of this lane is centroid cbase + (g & 3) + 8 (g >> 2) + 4 h
   float cn[16];
@@ -384,32 +332,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     const int c = cbase + (g & 3) + 8 * (g >> 2) + 4 * h;
     cn[g] = c < K ? cnorm[c] : INFINITY;
   }
-  const int srow = tid >> 3;
-  const int cq = (tid & 7) ^ ((srow >> 1) & 7);              // SOURCE chunk of this lane (LDS slot = tid & 7)
+  const SlicRtLane ln = slic_rt_lane(tid, D);
   const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(
       (void*)(Xp + pbeg * (int64_t)ldx), 0, prow > 0 ? (int)(((prow - 1) * (int64_t)ldx + D) * 4) : 0, 0x00020000);
-  constexpr unsigned OOB = 0xFFFFFF00u;
   unsigned xoff[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) xoff[i] = ((unsigned)(srow + 32 * i) * (unsigned)ldx + cq * 4) * 4u;
-  const int klim = D - cq * 4;
+  slic_rt_offsets(xoff, ln, (unsigned)ldx * 4u);
   // ring step (tile, kt): rows past the slice (the ragged last tile, the ring running past the last tile) lie past the buffer
   // resource's range and come back as zeros by themselves; k-tiles past D are sent out of range explicitly
-  auto issue = [&](int tile, int kt, int stage) {
-    float* Xs = km_lds + stage * STAGE_FLOATS;
-    const bool kin = kt * KM_BK < klim;
-    const unsigned kb = (unsigned)kt * (KM_BK * 4u);
-    const unsigned tb = (unsigned)tile * (unsigned)(BP * ldx * 4);
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_x, (__attribute__((address_space(3))) void*)(Xs + (8 * wave + 32 * i) * KM_BK),
-                                               16, (int)(kin ? tb + xoff[i] + kb : OOB), 0, 0, 0);
+  auto issue = [&](int tile, int kt) {
+    slic_rt_issue(rs_x, km_lds + (kt % ST) * SLIC_RT_TILE, wave, xoff, (unsigned)tile * (unsigned)(BP * ldx * 4), kt, ln.kin(kt));
   };
   KMS(unsigned long long kc_[4] = {0, 0, 0, 0}; const unsigned long long kt00_ = km_now();)
   f32x16 acc[4];                                               // 4 point sub-tiles of 32 x this wave's 32 centroids
   f32x4 b[2][4];                                               // point fragments, double-buffered ACROSS k-tiles
   int64_t op0 = -1;                                            // first point of the finished tile (its lists leave one step later)
-  float* xch = km_lds + ST * STAGE_FLOATS;                     // [wave 4][point 128] {score, index} of the finished tile
+  float* xch = km_lds + ST * SLIC_RT_TILE;                     // [wave 4][point 128] {score, index} of the finished tile
   // wave w's quarter of the finished tile: min over the four groups, ascending (first minimum wins: lower centroid index), and out
   auto flush = [&]() {
     const int64_t pq = op0 + 32 * wave + r;
@@ -423,12 +360,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     }
     if (h == 0 && pq < pend) { pscore[(int64_t)blockIdx.y * N + pq] = best; pidx[(int64_t)blockIdx.y * N + pq] = bidx; }
   };
-#pragma unroll
-  for (int u = 0; u < ST - 1; ++u) issue(u / NK, u % NK, u);   // steps 0 .. ST - 2
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4 * (ST - 2)) : "memory");             // step 0 has landed
-  __builtin_amdgcn_s_barrier();
-#pragma unroll
-  for (int pt = 0; pt < 4; ++pt) b[0][pt] = *(const f32x4*)&km_lds[km_off(32 * pt + r, h)];
+  slic_rt_ring_prime<ST>(b, km_lds, r, h, [&](int kn) SLIC_RT_INLINE { issue(0, kn); });
   KMS(kc_[0] = km_now() - kt00_;)
   auto tile_body = [&](const int tile, auto npt_) {
     constexpr int NPT = decltype(npt_)::value;                 // 32-point sub-tiles of this tile
@@ -437,42 +369,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     for (int pt = 0; pt < 4; ++pt)
 #pragma unroll
       for (int g = 0; g < 16; ++g) acc[pt][g] = 0.f;
+    // (stores of the previous tile's results may sit between the ring's DMAs: they only make the counted wait stricter.  LGKM: this
+    //  wave's ds_writes of the previous tile's (score, index) pairs — xch — must have reached LDS before the barrier of kt = 0 that
+    //  publishes them to the other waves' flush())
+    auto step = [&](int kn) SLIC_RT_INLINE { issue(kn >= NK ? tile + 1 : tile, kn >= NK ? kn - NK : kn); };
+    // the previous tile's partial argmin: combined and written HERE (behind the barrier that makes every wave's pairs visible), a whole
+    // k-tile before the next vmcnt wait, not in front of it
+    auto lists = [&](int kt) SLIC_RT_INLINE { if (kt == 0 && op0 >= 0) flush(); };
 #pragma unroll
-    for (int kt = 0; kt < NK; ++kt) {
-      // step s = (tile, kt) computes from stage kt % ST.  Outstanding loads here: the DMAs of steps s + 1 .. s + ST - 2 (4 each);
-      // stores of the previous tile's results may sit between them — they only make the wait stricter.
-      // (lgkmcnt(0): this wave's ds_writes of the previous tile's (score, index) pairs — xch — must have reached LDS before the barrier
-      //  that publishes them to the other waves' flush(); gfx950's back-off barrier does not imply it)
-      asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(4 * (ST - 3)) : "memory");         // step s + 1 has landed
-      __builtin_amdgcn_s_barrier();
-      {
-        const int kn = kt + ST - 1;                             // step s + ST - 1
-        issue(kn >= NK ? tile + 1 : tile, kn >= NK ? kn - NK : kn, kn % ST);
-      }
-      // the previous tile's partial argmin: combined and written HERE (behind the barrier that makes every wave's pairs visible), a whole
-      // k-tile before the next vmcnt wait, not in front of it
-      if (kt == 0 && op0 >= 0) flush();
-      const float* Xs = km_lds + (kt % ST) * STAGE_FLOATS;
-      const float* Xn = km_lds + ((kt + 1) % ST) * STAGE_FLOATS;
-      __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int cur = q & 1, nxt = cur ^ 1;
-#pragma unroll
-        for (int pt = 0; pt < 4; ++pt)                          // (all four: the step after a tile's last belongs to a full tile)
-          b[nxt][pt] = q < 3 ? *(const f32x4*)&Xs[km_off(32 * pt + r, 2 * (q + 1) + h)]
-                             : *(const f32x4*)&Xn[km_off(32 * pt + r, h)];        // first fragments of the next step
-        // k order inside every accumulator: q ascending, t ascending, lane half 0 then 1 => k ascending (permuted operands)
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-          for (int pt = 0; pt < NPT; ++pt)
-            acc[pt] = __builtin_amdgcn_mfma_f32_32x32x2f32(cr[kt][q][t], b[cur][pt][t], acc[pt], 0, 0, 0);
-        __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
-        __builtin_amdgcn_sched_group_barrier(0x008, 4 * NPT, 0);
-      }
-      __builtin_amdgcn_s_setprio(0);
-    }
+    for (int kt = 0; kt < NK; ++kt) slic_rt_ring_ktile<ST, true, NPT, true>(kt, acc, b, cr, km_lds, r, h, step, lists);
     KMS(const unsigned long long kb_ = km_now(); kc_[1] += kb_ - ka_;)
     // argmin over this wave's 32 centroids: ascending index inside the lane, then across the two lane halves; '<' / lower index
 #pragma unroll
@@ -508,7 +413,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     __syncthreads();
     flush();
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");             // the trailing all-zero DMAs must land before the workgroup leaves
+  slic_rt_wait<0>();                                           // the trailing all-zero DMAs must land before the workgroup leaves
   KMS(kc_[3] = km_now() - kt00_; if (lane == 0) for (int i_ = 0; i_ < 4; ++i_) atomicAdd(&km_cnt[i_], kc_[i_]);)
 }
 
@@ -1560,7 +1465,7 @@ __global__ __launch_bounds__(256) void kpp_dist_mfma(const float* __restrict__ X
                                                      float* __restrict__ newdist, double* __restrict__ bpart, int64_t nchunk) {
   extern __shared__ __attribute__((aligned(16))) float km_lds[];
   constexpr int BP = 128;
-  constexpr int STAGE_FLOATS = (BP + 32) * KM_BK;
+  constexpr int STAGE_FLOATS = (BP + 32) * SLIC_RT_BK;
   __shared__ float cn[PP_TMAX];
   __shared__ double wp[4][PP_TMAX];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -1580,17 +1485,17 @@ __global__ __launch_bounds__(256) void kpp_dist_mfma(const float* __restrict__ X
   const unsigned coff = srow < T ? ((unsigned)cand[srow] * (unsigned)ldx + cq * 4) * 4u : OOB;     // candidate row `srow`
   if (tid < T) cn[tid] = xnorm[cand[tid]];
   const int klim = D - cq * 4;
-  const int nk = (D + KM_BK - 1) / KM_BK;
+  const int nk = (D + SLIC_RT_BK - 1) / SLIC_RT_BK;
   auto issue = [&](int kt, int stage) {
     float* Xs = km_lds + stage * STAGE_FLOATS;
-    float* Cs = Xs + BP * KM_BK;
-    const bool kin = kt * KM_BK < klim;
-    const unsigned kb = (unsigned)kt * (KM_BK * 4u);
+    float* Cs = Xs + BP * SLIC_RT_BK;
+    const bool kin = kt * SLIC_RT_BK < klim;
+    const unsigned kb = (unsigned)kt * (SLIC_RT_BK * 4u);
 #pragma unroll
     for (int i = 0; i < 4; ++i)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_x, (__attribute__((address_space(3))) void*)(Xs + (8 * wave + 32 * i) * KM_BK),
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_x, (__attribute__((address_space(3))) void*)(Xs + (8 * wave + 32 * i) * SLIC_RT_BK),
                                                16, (int)((kin && xoff[i] != OOB) ? xoff[i] + kb : OOB), 0, 0, 0);
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_c, (__attribute__((address_space(3))) void*)(Cs + (8 * wave) * KM_BK),
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_c, (__attribute__((address_space(3))) void*)(Cs + (8 * wave) * SLIC_RT_BK),
                                              16, (int)((kin && coff != OOB) ? coff + kb : OOB), 0, 0, 0);
   };
   f32x16 acc;
@@ -1606,11 +1511,11 @@ __global__ __launch_bounds__(256) void kpp_dist_mfma(const float* __restrict__ X
       __builtin_amdgcn_s_barrier();
       issue(s0 + sidx + 1, sidx ^ 1);
       const float* Xs = km_lds + sidx * STAGE_FLOATS;
-      const float* Cs = Xs + BP * KM_BK;
+      const float* Cs = Xs + BP * SLIC_RT_BK;
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-        const f32x4 b = *(const f32x4*)&Xs[km_off(32 * wave + r, 2 * q + h)];
-        const f32x4 a = *(const f32x4*)&Cs[km_off(r, 2 * q + h)];
+        const f32x4 b = *(const f32x4*)&Xs[slic_rt_off(32 * wave + r, 2 * q + h)];
+        const f32x4 a = *(const f32x4*)&Cs[slic_rt_off(r, 2 * q + h)];
 #pragma unroll
         for (int t = 0; t < 4; ++t) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[t], b[t], acc, 0, 0, 0);
       }
@@ -1769,7 +1674,7 @@ __global__ __launch_bounds__(256) void kpp_dist_mfma_batch(const float* __restri
                                                            float* __restrict__ newdist, double* __restrict__ bpart, int64_t nchunk) {
   extern __shared__ __attribute__((aligned(16))) float km_lds[];
   constexpr int BP = 128, CR = 32 * NG;
-  constexpr int STAGE_FLOATS = (BP + CR) * KM_BK;
+  constexpr int STAGE_FLOATS = (BP + CR) * SLIC_RT_BK;
   __shared__ float cn[CR];
   __shared__ double wp[4][CR];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -1790,19 +1695,19 @@ __global__ __launch_bounds__(256) void kpp_dist_mfma_batch(const float* __restri
   for (int g = 0; g < NG; ++g) coff[g] = (srow + 32 * g) < RT ? ((unsigned)cand[srow + 32 * g] * (unsigned)ldx + cq * 4) * 4u : OOB;
   for (int q = tid; q < CR; q += 256) cn[q] = q < RT ? xnorm[cand[q]] : 0.f;
   const int klim = D - cq * 4;
-  const int nk = (D + KM_BK - 1) / KM_BK;
+  const int nk = (D + SLIC_RT_BK - 1) / SLIC_RT_BK;
   auto issue = [&](int kt, int stage) {
     float* Xs = km_lds + stage * STAGE_FLOATS;
-    float* Cs = Xs + BP * KM_BK;
-    const bool kin = kt * KM_BK < klim;
-    const unsigned kb = (unsigned)kt * (KM_BK * 4u);
+    float* Cs = Xs + BP * SLIC_RT_BK;
+    const bool kin = kt * SLIC_RT_BK < klim;
+    const unsigned kb = (unsigned)kt * (SLIC_RT_BK * 4u);
 #pragma unroll
     for (int i = 0; i < 4; ++i)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_x, (__attribute__((address_space(3))) void*)(Xs + (8 * wave + 32 * i) * KM_BK),
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_x, (__attribute__((address_space(3))) void*)(Xs + (8 * wave + 32 * i) * SLIC_RT_BK),
                                                16, (int)((kin && xoff[i] != OOB) ? xoff[i] + kb : OOB), 0, 0, 0);
 #pragma unroll
     for (int g = 0; g < NG; ++g)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_c, (__attribute__((address_space(3))) void*)(Cs + (8 * wave + 32 * g) * KM_BK),
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_c, (__attribute__((address_space(3))) void*)(Cs + (8 * wave + 32 * g) * SLIC_RT_BK),
                                                16, (int)((kin && coff[g] != OOB) ? coff[g] + kb : OOB), 0, 0, 0);
   };
   f32x16 acc[NG];
@@ -1819,13 +1724,13 @@ __global__ __launch_bounds__(256) void kpp_dist_mfma_batch(const float* __restri
       __builtin_amdgcn_s_barrier();
       issue(s0 + sidx + 1, sidx ^ 1);
       const float* Xs = km_lds + sidx * STAGE_FLOATS;
-      const float* Cs = Xs + BP * KM_BK;
+      const float* Cs = Xs + BP * SLIC_RT_BK;
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-        const f32x4 b = *(const f32x4*)&Xs[km_off(32 * wave + r, 2 * q + h)];
+        const f32x4 b = *(const f32x4*)&Xs[slic_rt_off(32 * wave + r, 2 * q + h)];
 #pragma unroll
         for (int g = 0; g < NG; ++g) {
-          const f32x4 a = *(const f32x4*)&Cs[km_off(32 * g + r, 2 * q + h)];
+          const f32x4 a = *(const f32x4*)&Cs[slic_rt_off(32 * g + r, 2 * q + h)];
 #pragma unroll
           for (int t = 0; t < 4; ++t) acc[g] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[t], b[t], acc[g], 0, 0, 0);
         }
@@ -1999,7 +1904,7 @@ template <int BP, int NCT, int WC, int STAGES>
 static int launch_assign_dma(const float* Xp, int64_t N, int D, int ldx, const float* Cp, int K, int ldc,
                              const float* cnorm, float* pscore, int32_t* pidx, hipStream_t st, int32_t* z0 = nullptr,
                              int32_t* z1 = nullptr) {
-  const size_t lds = (size_t)STAGES * (BP + NCT * 32) * KM_BK * sizeof(float);
+  const size_t lds = (size_t)STAGES * (BP + NCT * 32) * SLIC_RT_BK * sizeof(float);
   SLIC_LDS_LIMIT((km_assign_dma<BP, NCT, WC, STAGES>), lds);
   dim3 grid((unsigned)slic_cdiv(N, BP), (unsigned)slic_cdiv(K, NCT * 32));
   km_assign_dma<BP, NCT, WC, STAGES><<<grid, dim3(256), lds, st>>>(Xp, N, D, ldx, Cp, K, ldc, cnorm, pscore, pidx, z0, z1);
@@ -2055,7 +1960,7 @@ static int km_assign_perm_impl(const float* Xp, int64_t N, int D, int ldx, const
                     tiles * 4 >= km_creg_min_quarter_tiles() * (int64_t)slices &&             // enough points per workgroup to pay for loading its centroids
                     (slic_cdiv(tiles, slices) * 128 + 128) * (int64_t)ldx * 4 < (1ll << 31);        // slice inside one resource
   if (creg) {
-    const size_t lds = (size_t)4 * 128 * KM_BK * sizeof(float) + 4 * 128 * 2 * sizeof(float);     // the ring + the tile's four pair lists
+    const size_t lds = (size_t)4 * 128 * SLIC_RT_BK * sizeof(float) + 4 * 128 * 2 * sizeof(float);     // the ring + the tile's four pair lists
     dim3 grid((unsigned)slices, (unsigned)ncb);
     const auto kern = D > 256 ? km_assign_creg<16, 4> : D > 128 ? km_assign_creg<8, 4> : km_assign_creg<4, 4>;
     SLIC_LDS_LIMIT(kern, lds);
@@ -2400,7 +2305,7 @@ extern "C" int slic_kmeanspp_run(const float* X, int64_t N, int D, int ldx, int 
   int32_t* sel = w.take<int32_t>(1);
   // matrix-pipe distances when the caller has the k-permuted copy and the row norms (and 32-bit offsets reach every row)
   const bool mfma = Xp && xnorm && D % 8 == 0 && (int64_t)N * ldx * 4 < (1ll << 31);
-  const size_t lds_m = (size_t)2 * (128 + 32) * KM_BK * sizeof(float);
+  const size_t lds_m = (size_t)2 * (128 + 32) * SLIC_RT_BK * sizeof(float);
   if (mfma) SLIC_LDS_LIMIT(kpp_dist_mfma, lds_m);
   const unsigned nblk_m = (unsigned)slic_cdiv(N, 128);
   // centre 0: one candidate (the uniformly drawn row), no closest yet
@@ -2454,7 +2359,7 @@ extern "C" int slic_kmeanspp_run_batch(const float* Xp, const float* xnorm, int6
   const unsigned nblk_m = (unsigned)slic_cdiv(N, 128);
   auto dist = [&](int RT, int Tc, int Tprev, const int32_t* cand, const float* prev, float* cur) -> int {
     const int ng = (RT + 31) / 32;
-    const size_t lds = (size_t)2 * (128 + 32 * ng) * KM_BK * sizeof(float);
+    const size_t lds = (size_t)2 * (128 + 32 * ng) * SLIC_RT_BK * sizeof(float);
 #define KPP_BATCH(NG)                                                                                                              \
     {                                                                                                                              \
       SLIC_LDS_LIMIT(kpp_dist_mfma_batch<NG>, lds);                                                                                \

@@ -13,20 +13,15 @@
 // expectation.  Order: larger s first, ties -> lower gallery index.
 // slic_topk_merge folds the per-slice lists into the final sorted [Nq, k].
 // The same kernels serve euclidean top-k (slic_euclidean_topk, at the end of this file) through their EU instantiations.
-#include "common.h"
+#include "mfma_ring.h"
 #include <math.h>
 #include <limits.h>
 #include <stdlib.h>
 
 #define TK_BQ 128
 #define TK_BG 128
-#define TK_BK 32
 #define TK_PC_MAX 32   // pending candidates per lane between heap drains (fewer when k leaves less LDS)
 #define TK_KMAX 88
-
-__device__ __forceinline__ int tk_off(int row, int chunk) {
-  return row * TK_BK + ((chunk ^ ((row >> 1) & 7)) << 2);
-}
 
 // (score, gallery index) as ONE 64-bit key whose unsigned order is the retrieval order — larger score first, ties -> lower
 // index: high word = the order-preserving image of the float, low word = ~index.  A heap step then costs one 8-byte LDS access
@@ -46,6 +41,30 @@ __device__ __forceinline__ bool tk_better(float s, int i, float t, int ti) {
   return s > t || (s == t && i < ti);
 }
 
+// Insert `cand` (better than `root`) into query r's heap hp[e * 32 + r], e < kh, and update `root`.  4-ary heap, root (slot 0) = worst
+// kept entry: the four children of a node are read together (one LDS round trip per level, log4 k levels), the worst of them moves
+// up while it is worse than the candidate.
+__device__ __forceinline__ void tk_heap_push(unsigned long long* hp, int r, int kh, unsigned long long cand, unsigned long long& root) {
+  int pos = 0;
+  unsigned long long newroot = cand;
+  for (;;) {
+    const int c0 = 4 * pos + 1;
+    if (c0 >= kh) break;
+    const unsigned long long k0 = hp[c0 * 32 + r], k1 = hp[(c0 + 1) * 32 + r], k2 = hp[(c0 + 2) * 32 + r],
+                             k3 = hp[(c0 + 3) * 32 + r];
+    unsigned long long w = k0; int ws = c0;
+    if (k1 < w) { w = k1; ws = c0 + 1; }
+    if (k2 < w) { w = k2; ws = c0 + 2; }
+    if (k3 < w) { w = k3; ws = c0 + 3; }
+    if (!(cand > w)) break;
+    hp[pos * 32 + r] = w;
+    if (pos == 0) newroot = w;
+    pos = ws;
+  }
+  hp[pos * 32 + r] = cand;
+  root = newroot;
+}
+
 // EU (every partial / collect kernel below): the euclidean ranking score s = q.g - |g|^2 / 2 instead of the cosine q.g — for a fixed
 // query the same order as ascending |q - g|.  The accumulators of a tile start at -ghn[row] (ghn: [Ng] half squared norms of the gallery
 // rows) instead of 0; the k loop, the masks and the scan are the same.  Cosine (EU = false) never reads ghn.
@@ -56,7 +75,7 @@ __global__ __launch_bounds__(256) void topk_partial_kernel(
     const float* __restrict__ ghn) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   float* stage = lds;                                   // [2][2][128*32]
-  float* lval = lds + 2 * 2 * TK_BQ * TK_BK;             // [4 waves][k][32]
+  float* lval = lds + 2 * 2 * TK_BQ * SLIC_RT_BK;             // [4 waves][k][32]
   int* lidx = (int*)(lval + 4 * k * 32);
   float* pval_l = (float*)(lidx + 4 * k * 32);          // [4 waves][TK_PC][32] pending candidates (value)
   int* pidx_l = (int*)(pval_l + 4 * TK_PC * 32);        // [4 waves][TK_PC][32]              (gallery index)
@@ -84,7 +103,7 @@ __global__ __launch_bounds__(256) void topk_partial_kernel(
     if (qq > Nq - 1) qq = Nq - 1;
     qr[p] = Q + (int64_t)qq * D + scp * 8;
   }
-  const int nk = (D + TK_BK - 1) / TK_BK;
+  const int nk = (D + SLIC_RT_BK - 1) / SLIC_RT_BK;
   const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
 
   for (int g0 = gbeg; g0 < gend; g0 += TK_BG) {
@@ -99,7 +118,7 @@ __global__ __launch_bounds__(256) void topk_partial_kernel(
     }
     f32x4 xq[2][2], xg[2][2];
     auto gload = [&](int kt) {
-      const int k0 = kt * TK_BK;
+      const int k0 = kt * SLIC_RT_BK;
       const bool kin = (k0 + scp * 8) < D;
 #pragma unroll
       for (int p = 0; p < 2; ++p) {
@@ -110,15 +129,15 @@ __global__ __launch_bounds__(256) void topk_partial_kernel(
       }
     };
     auto lwrite = [&](int buf) {
-      float* Gs = stage + (buf * 2 + 0) * TK_BQ * TK_BK;
-      float* Qs = stage + (buf * 2 + 1) * TK_BQ * TK_BK;
+      float* Gs = stage + (buf * 2 + 0) * TK_BQ * SLIC_RT_BK;
+      float* Qs = stage + (buf * 2 + 1) * TK_BQ * SLIC_RT_BK;
 #pragma unroll
       for (int p = 0; p < 2; ++p) {
         const int row = srow + 64 * p;
-        *(f32x4*)&Qs[tk_off(row, 2 * scp)] = xq[p][0];
-        *(f32x4*)&Qs[tk_off(row, 2 * scp + 1)] = xq[p][1];
-        *(f32x4*)&Gs[tk_off(row, 2 * scp)] = xg[p][0];
-        *(f32x4*)&Gs[tk_off(row, 2 * scp + 1)] = xg[p][1];
+        *(f32x4*)&Qs[slic_rt_off(row, 2 * scp)] = xq[p][0];
+        *(f32x4*)&Qs[slic_rt_off(row, 2 * scp + 1)] = xq[p][1];
+        *(f32x4*)&Gs[slic_rt_off(row, 2 * scp)] = xg[p][0];
+        *(f32x4*)&Gs[slic_rt_off(row, 2 * scp + 1)] = xg[p][1];
       }
     };
     f32x16 acc[4];
@@ -138,14 +157,14 @@ __global__ __launch_bounds__(256) void topk_partial_kernel(
     for (int kt = 0; kt < nk; ++kt) {
       const int buf = kt & 1;
       if (kt + 1 < nk) gload(kt + 1);
-      const float* Gs = stage + (buf * 2 + 0) * TK_BQ * TK_BK;
-      const float* Qs = stage + (buf * 2 + 1) * TK_BQ * TK_BK;
+      const float* Gs = stage + (buf * 2 + 0) * TK_BQ * SLIC_RT_BK;
+      const float* Qs = stage + (buf * 2 + 1) * TK_BQ * SLIC_RT_BK;
 #pragma unroll
       for (int qd = 0; qd < 4; ++qd) {
-        const f32x4 b = *(const f32x4*)&Qs[tk_off(32 * wave + r, 2 * qd + h)];
+        const f32x4 b = *(const f32x4*)&Qs[slic_rt_off(32 * wave + r, 2 * qd + h)];
         f32x4 a[4];
 #pragma unroll
-        for (int ct = 0; ct < 4; ++ct) a[ct] = *(const f32x4*)&Gs[tk_off(32 * ct + r, 2 * qd + h)];
+        for (int ct = 0; ct < 4; ++ct) a[ct] = *(const f32x4*)&Gs[slic_rt_off(32 * ct + r, 2 * qd + h)];
 #pragma unroll
         for (int t = 0; t < 4; ++t)
 #pragma unroll
@@ -261,7 +280,7 @@ __global__ __launch_bounds__(256) void topk_partial_dma(
     const float* __restrict__ ghn) {
   TKC_DECL
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  constexpr int STAGE_FLOATS = (TK_BQ + TK_BG) * TK_BK;
+  constexpr int STAGE_FLOATS = 2 * SLIC_RT_TILE;               // gallery tile, then query tile
   // heaps: [4 waves][kh][32] keys, kh = k rounded up to 4 m + 1 so that every node has four children (the padding holds the
   // best possible key and is never picked as a node's worst child); pending candidates: [4 waves][TK_PC][64] keys, one column per LANE
   const int kh = 1 + ((k + 2) / 4) * 4;
@@ -289,64 +308,29 @@ __global__ __launch_bounds__(256) void topk_partial_dma(
   unsigned long long root = KEY_EMPTY;                       // worst kept entry (heap root)
   float thr = owner ? -INFINITY : INFINITY;                  // its score; +inf on lanes that own no list: never a candidate
 
-  const int srow = tid >> 3;
-  const int cq = (tid & 7) ^ ((srow >> 1) & 7);              // SOURCE chunk of this lane (LDS slot = tid & 7)
+  const SlicRtLane ln = slic_rt_lane(tid, D);
   const int qrows = min(TK_BQ, Nq - q0);
   const __amdgpu_buffer_rsrc_t rs_q = __builtin_amdgcn_make_buffer_rsrc(
       (void*)(Q + (int64_t)q0 * D), 0, (int)((int64_t)qrows * D * 4), 0x00020000);
   const __amdgpu_buffer_rsrc_t rs_g = __builtin_amdgcn_make_buffer_rsrc(
       (void*)(G + (int64_t)gbeg * D), 0, (int)((int64_t)(gend - gbeg) * D * 4), 0x00020000);     // rows past the slice: zeros
-  constexpr unsigned OOB = 0xFFFFFF00u;
   unsigned qoff[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) qoff[i] = ((unsigned)(srow + 32 * i) * (unsigned)D + cq * 4) * 4u;
-  const int klim = D - cq * 4;
-  const int nk = (D + TK_BK - 1) / TK_BK;
+  slic_rt_offsets(qoff, ln, (unsigned)D * 4u);
+  const int nk = (D + SLIC_RT_BK - 1) / SLIC_RT_BK;
   const int nkp = (nk + 1) & ~1;                              // k-tiles per gallery tile, rounded up to the ring length
   const int ntile = (gend - gbeg + TK_BG - 1) / TK_BG;
   // issue the DMAs of ring step (tile, kt) — kt may run into the zero padding, tile past the end is all out of range
   auto issue = [&](int tile, int kt, int stage) {
     float* Gs = lds + stage * STAGE_FLOATS;
-    float* Qs = Gs + TK_BG * TK_BK;
-    const bool kin = kt * TK_BK < klim && tile < ntile;
-    const unsigned kb = (unsigned)kt * (TK_BK * 4u);
-    const unsigned gb = (unsigned)tile * (unsigned)(TK_BG * D * 4);
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_g, (__attribute__((address_space(3))) void*)(Gs + (8 * wave + 32 * i) * TK_BK),
-                                               16, (int)(kin ? gb + qoff[i] + kb : OOB), 0, 0, 0);
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_q, (__attribute__((address_space(3))) void*)(Qs + (8 * wave + 32 * i) * TK_BK),
-                                               16, (int)(kin ? qoff[i] + kb : OOB), 0, 0, 0);
+    const bool live = ln.kin(kt) && tile < ntile;
+    slic_rt_issue(rs_g, Gs, wave, qoff, (unsigned)tile * (unsigned)(TK_BG * D * 4), kt, live);
+    slic_rt_issue(rs_q, Gs + SLIC_RT_TILE, wave, qoff, 0u, kt, live);
   };
   f32x16 acc[4];
   int gimg = (int)0x807FFFFF;                                  // order-preserving int image of -inf
   auto compute = [&](int stage) {
     const float* Gs = lds + stage * STAGE_FLOATS;
-    const float* Qs = Gs + TK_BG * TK_BK;
-    f32x4 b[2], a[2][4];
-    b[0] = *(const f32x4*)&Qs[tk_off(32 * wave + r, h)];
-#pragma unroll
-    for (int ct = 0; ct < 4; ++ct) a[0][ct] = *(const f32x4*)&Gs[tk_off(32 * ct + r, h)];
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int qd = 0; qd < 4; ++qd) {
-      const int cur = qd & 1, nxt = cur ^ 1;
-      if (qd < 3) {
-        b[nxt] = *(const f32x4*)&Qs[tk_off(32 * wave + r, 2 * (qd + 1) + h)];
-#pragma unroll
-        for (int ct = 0; ct < 4; ++ct) a[nxt][ct] = *(const f32x4*)&Gs[tk_off(32 * ct + r, 2 * (qd + 1) + h)];
-      }
-#pragma unroll
-      for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int ct = 0; ct < 4; ++ct)
-          acc[ct] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[cur][ct][t], b[cur][t], acc[ct], 0, 0, 0);
-      if (qd < 3) __builtin_amdgcn_sched_group_barrier(0x100, 5, 0);
-      __builtin_amdgcn_sched_group_barrier(0x008, 16, 0);
-    }
-    __builtin_amdgcn_s_setprio(0);
+    slic_rt_compute_stage<4>(acc, Gs + SLIC_RT_TILE, Gs, 0, 32 * wave, r, h);
   };
   auto flush = [&]() {
     const int pcp = __shfl_xor(pc, 32);                        // the partner half's count
@@ -363,26 +347,7 @@ __global__ __launch_bounds__(256) void topk_partial_dma(
 #if defined(TK_COUNT) && TK_COUNT > 1
           atomicAdd(&tk_cnt[5], 1ull);
 #endif
-          // 4-ary heap, root (slot 0) = worst kept entry: the four children of a node are read together (one LDS round
-          // trip per level, log4 k levels), the worst of them moves up while it is worse than the candidate
-          int pos = 0;
-          unsigned long long newroot = cand;
-          for (;;) {
-            const int c0 = 4 * pos + 1;
-            if (c0 >= kh) break;
-            const unsigned long long k0 = hp[c0 * 32 + r], k1 = hp[(c0 + 1) * 32 + r], k2 = hp[(c0 + 2) * 32 + r],
-                                     k3 = hp[(c0 + 3) * 32 + r];
-            unsigned long long w = k0; int ws = c0;
-            if (k1 < w) { w = k1; ws = c0 + 1; }
-            if (k2 < w) { w = k2; ws = c0 + 2; }
-            if (k3 < w) { w = k3; ws = c0 + 3; }
-            if (!(cand > w)) break;
-            hp[pos * 32 + r] = w;
-            if (pos == 0) newroot = w;
-            pos = ws;
-          }
-          hp[pos * 32 + r] = cand;
-          root = newroot;
+          tk_heap_push(hp, r, kh, cand, root);
         }
       }
     }
@@ -415,7 +380,7 @@ __global__ __launch_bounds__(256) void topk_partial_dma(
 #pragma unroll
       for (int sidx = 0; sidx < 2; ++sidx) {
         const int kt = s0 + sidx;
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        slic_rt_wait<0>();
         __builtin_amdgcn_s_barrier();
         const bool wrap = kt + 1 >= nkp;                       // the next ring step opens the next gallery tile
         issue(wrap ? tile + 1 : tile, wrap ? 0 : kt + 1, sidx ^ 1);
@@ -493,7 +458,7 @@ __global__ __launch_bounds__(256) void topk_partial_dma(
   }
   flush();
   TKC_FLUSH;
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  slic_rt_wait<0>();
   if (h == 0 && q < Nq) {
     float* ov = pval + ((int64_t)blockIdx.y * Nq + q) * k;
     int32_t* oi = pidx + ((int64_t)blockIdx.y * Nq + q) * k;
@@ -555,7 +520,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     Nq = *nq_dev;
     if ((int)blockIdx.x * TK_BQ >= Nq) return;                 // (workgroup-uniform, before any barrier)
   }
-  constexpr int STAGE_FLOATS = TK_BG * TK_BK;                  // gallery rows only
+  constexpr int STAGE_FLOATS = TK_BG * SLIC_RT_BK;                  // gallery rows only
   const int kh = 1 + ((k + 2) / 4) * 4;
   unsigned long long* heaps = (unsigned long long*)(lds + 4 * STAGE_FLOATS);
   unsigned long long* pend = heaps + 4 * kh * 32;
@@ -618,12 +583,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   // the DMAs of ring step (tile, kt): k-tiles past D are all-zero, a tile past the end is all out of range
   auto issue = [&](int tile, int kt, int stage) {
     float* Gs = lds + stage * STAGE_FLOATS;
-    const bool kin = kt * TK_BK < klim && tile < ntile;
-    const unsigned kb = (unsigned)kt * (TK_BK * 4u);
+    const bool kin = kt * SLIC_RT_BK < klim && tile < ntile;
+    const unsigned kb = (unsigned)kt * (SLIC_RT_BK * 4u);
     const unsigned gb = (unsigned)tile * ((unsigned)TK_BG * rowb);
 #pragma unroll
     for (int i = 0; i < 4; ++i)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_g, (__attribute__((address_space(3))) void*)(Gs + (8 * wave + 32 * i) * TK_BK),
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_g, (__attribute__((address_space(3))) void*)(Gs + (8 * wave + 32 * i) * SLIC_RT_BK),
                                                16, (int)(kin ? gb + goff[i] + kb : OOB), 0, 0, 0);
   };
   auto flush = [&]() {
@@ -638,24 +603,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         const int jj = j < pc ? j : j - pc;
         const unsigned long long cand = pq[jj * 64 + (j < pc ? lane : lane + 32)];
         if (cand > root) {
-          int pos = 0;                                         // 4-ary heap, see topk_partial_dma
-          unsigned long long newroot = cand;
-          for (;;) {
-            const int c0 = 4 * pos + 1;
-            if (c0 >= kh) break;
-            const unsigned long long k0 = hp[c0 * 32 + r], k1 = hp[(c0 + 1) * 32 + r], k2 = hp[(c0 + 2) * 32 + r],
-                                     k3 = hp[(c0 + 3) * 32 + r];
-            unsigned long long w = k0; int ws = c0;
-            if (k1 < w) { w = k1; ws = c0 + 1; }
-            if (k2 < w) { w = k2; ws = c0 + 2; }
-            if (k3 < w) { w = k3; ws = c0 + 3; }
-            if (!(cand > w)) break;
-            hp[pos * 32 + r] = w;
-            if (pos == 0) newroot = w;
-            pos = ws;
-          }
-          hp[pos * 32 + r] = cand;
-          root = newroot;
+          tk_heap_push(hp, r, kh, cand, root);
         }
       }
     }
@@ -676,7 +624,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   asm volatile("s_waitcnt vmcnt(8)" ::: "memory");             // step 0 has landed
   __builtin_amdgcn_s_barrier();
 #pragma unroll
-  for (int ct = 0; ct < 4; ++ct) a[0][ct] = *(const f32x4*)&lds[tk_off(32 * ct + r, h)];
+  for (int ct = 0; ct < 4; ++ct) a[0][ct] = *(const f32x4*)&lds[slic_rt_off(32 * ct + r, h)];
   for (int tile = 0; tile < ntile; ++tile) {
 #ifdef TK_COUNT
     const unsigned long long ts0_ = tk_now();
@@ -714,8 +662,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         const int cur = qd & 1, nxt = cur ^ 1;
 #pragma unroll
         for (int ct = 0; ct < 4; ++ct)
-          a[nxt][ct] = qd < 3 ? *(const f32x4*)&Gs[tk_off(32 * ct + r, 2 * (qd + 1) + h)]
-                              : *(const f32x4*)&Gn[tk_off(32 * ct + r, h)];       // first fragments of the next step
+          a[nxt][ct] = qd < 3 ? *(const f32x4*)&Gs[slic_rt_off(32 * ct + r, 2 * (qd + 1) + h)]
+                              : *(const f32x4*)&Gn[slic_rt_off(32 * ct + r, h)];       // first fragments of the next step
 #pragma unroll
         for (int t = 0; t < 4; ++t)
 #pragma unroll
@@ -850,8 +798,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     const float* __restrict__ ghn /* EU: [Ng] half squared norms (see topk_partial_qreg) */) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   static_assert(NK % 4 == 0, "a gallery tile is a whole number of ring turns");
-  constexpr int STAGE_FLOATS = TK_BG * TK_BK;                  // gallery rows only
-  unsigned long long* pend = (unsigned long long*)(lds + 4 * STAGE_FLOATS);      // [4 waves][TK_PC][64] keys, one column per LANE
+  unsigned long long* pend = (unsigned long long*)(lds + 4 * SLIC_RT_TILE);      // [4 waves][TK_PC][64] keys, one column per LANE
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r = lane & 31, h = lane >> 5;
@@ -866,26 +813,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   // both halves of a lane pair serve query r and test against its threshold; slots past Nq never see a candidate
   const float filt = q < Nq ? tau[q] : INFINITY;
   f32x4 qr[NK][4];
-  {
-    const float* qrow = Q + (int64_t)(q < Nq ? q : Nq - 1) * D;
-#pragma unroll
-    for (int kt = 0; kt < NK; ++kt)
-#pragma unroll
-      for (int qd = 0; qd < 4; ++qd) {
-        const int c = 32 * kt + 8 * qd + 4 * h;
-        f32x4 z = {0.f, 0.f, 0.f, 0.f};
-        qr[kt][qd] = c < D ? *(const f32x4*)(qrow + c) : z;
-      }
-  }
-  const int srow = tid >> 3;
-  const int cq = (tid & 7) ^ ((srow >> 1) & 7);              // SOURCE chunk of this lane (LDS slot = tid & 7)
+  slic_rt_load_frags(qr, Q + (int64_t)(q < Nq ? q : Nq - 1) * D, D, h);
+  const SlicRtLane ln = slic_rt_lane(tid, D);
   const __amdgpu_buffer_rsrc_t rs_g = __builtin_amdgcn_make_buffer_rsrc(
       (void*)(G + (int64_t)gbeg * D), 0, (int)((int64_t)(gend - gbeg) * D * 4), 0x00020000);     // rows past the slice: zeros
-  constexpr unsigned OOB = 0xFFFFFF00u;
   unsigned goff[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) goff[i] = ((unsigned)(srow + 32 * i) * (unsigned)D + cq * 4) * 4u;
-  const int klim = D - cq * 4;
+  slic_rt_offsets(goff, ln, (unsigned)D * 4u);
   const int ntile = (gend - gbeg + TK_BG - 1) / TK_BG;
   auto bias_fetch = [&](int tile) {
 #pragma unroll
@@ -894,15 +827,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
       bn[u] = gi < gend ? ghn[gi] : 0.f;
     }
   };
-  auto issue = [&](int tile, int kt, int stage) {
-    float* Gs = lds + stage * STAGE_FLOATS;
-    const bool kin = kt * TK_BK < klim && tile < ntile;
-    const unsigned kb = (unsigned)kt * (TK_BK * 4u);
-    const unsigned gb = (unsigned)tile * (unsigned)(TK_BG * D * 4);
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_g, (__attribute__((address_space(3))) void*)(Gs + (8 * wave + 32 * i) * TK_BK),
-                                               16, (int)(kin ? gb + goff[i] + kb : OOB), 0, 0, 0);
+  auto issue = [&](int tile, int kt) {
+    const bool live = ln.kin(kt) && tile < ntile;
+    slic_rt_issue(rs_g, lds + (kt & 3) * SLIC_RT_TILE, wave, goff, (unsigned)tile * (unsigned)(TK_BG * D * 4), kt, live);
   };
   // a lane's pending keys -> the query's candidate buffer: ONE atomic add reserves the lane's slots (its return is the only round trip
   // to memory; a drain happens at the end of the slice and when a column runs full — every ~100 tiles at 400 candidates per query)
@@ -920,13 +847,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   f32x16 acc[4];
   f32x4 a[2][4];
   if constexpr (EU) bias_fetch(0);
-  issue(0, 0, 0);
-  issue(NK > 1 ? 0 : 1, NK > 1 ? 1 : 0, 1);
-  issue(NK > 2 ? 0 : 1, NK > 2 ? 2 : 0, 2);
-  asm volatile("s_waitcnt vmcnt(8)" ::: "memory");             // step 0 has landed
-  __builtin_amdgcn_s_barrier();
-#pragma unroll
-  for (int ct = 0; ct < 4; ++ct) a[0][ct] = *(const f32x4*)&lds[tk_off(32 * ct + r, h)];
+  slic_rt_ring_prime<4>(a, lds, r, h, [&](int kn) SLIC_RT_INLINE { issue(0, kn); });
   for (int tile = 0; tile < ntile; ++tile) {
     if constexpr (EU) tk_bias_init(acc, bw, bn, lane, h);
     else {
@@ -935,37 +856,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 #pragma unroll
         for (int v = 0; v < 16; ++v) acc[ct][v] = 0.f;
     }
-#pragma unroll
-    for (int kt = 0; kt < NK; ++kt) {
-      // (a drain's stores and atomic may sit among the outstanding DMAs: they only make this wait stricter)
-      asm volatile("s_waitcnt vmcnt(4)" ::: "memory");         // step s + 1 has landed (this wave's part of it)
-      __builtin_amdgcn_s_barrier();                            // ... everybody's; and stage (kt + 3) & 3 has been read by all
+    // (a drain's stores and atomic may sit among the outstanding DMAs: they only make the counted wait stricter)
+    auto step = [&](int kn) SLIC_RT_INLINE {
       if constexpr (EU)
-        if (kt == 1) bias_fetch(tile + 1);                     // (see topk_partial_qreg)
-      {
-        const int kn = kt + 3;
-        issue(kn >= NK ? tile + 1 : tile, kn >= NK ? kn - NK : kn, kn & 3);
-      }
-      const float* Gs = lds + (kt & 3) * STAGE_FLOATS;
-      const float* Gn = lds + ((kt + 1) & 3) * STAGE_FLOATS;
-      __builtin_amdgcn_s_setprio(1);
+        if (kn == 4) bias_fetch(tile + 1);                     // (see topk_partial_qreg)
+      issue(kn >= NK ? tile + 1 : tile, kn >= NK ? kn - NK : kn);
+    };
 #pragma unroll
-      for (int qd = 0; qd < 4; ++qd) {
-        const int cur = qd & 1, nxt = cur ^ 1;
-#pragma unroll
-        for (int ct = 0; ct < 4; ++ct)
-          a[nxt][ct] = qd < 3 ? *(const f32x4*)&Gs[tk_off(32 * ct + r, 2 * (qd + 1) + h)]
-                              : *(const f32x4*)&Gn[tk_off(32 * ct + r, h)];       // first fragments of the next step
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-          for (int ct = 0; ct < 4; ++ct)
-            acc[ct] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[cur][ct][t], qr[kt][qd][t], acc[ct], 0, 0, 0);
-        __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
-        __builtin_amdgcn_sched_group_barrier(0x008, 16, 0);
-      }
-      __builtin_amdgcn_s_setprio(0);
-    }
+    for (int kt = 0; kt < NK; ++kt) slic_rt_ring_ktile<4, false, 4, false>(kt, acc, a, qr, lds, r, h, step, [](int) SLIC_RT_INLINE {});
     const int g0 = gbeg + tile * TK_BG;
     const bool ragged = g0 + TK_BG > gend;
     const bool selfhit = self_mask && g0 < q0 + 32 * wave + 32 && g0 + TK_BG > q0 + 32 * wave;
@@ -1001,7 +899,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     }
   }
   drain();
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");             // the trailing all-zero DMAs must land before the workgroup leaves
+  slic_rt_wait<0>();                                           // the trailing all-zero DMAs must land before the workgroup leaves
 }
 
 // one WAVE per query: the k best of its n = cnt[q] candidate keys, best first.  n <= TKS_NP keys are sorted in LDS by the wave — a
@@ -1278,7 +1176,7 @@ static int topk_stream(const float* Qn, int Nq, const float* Gn, int Ng, int D, 
   int32_t* pidx = w.take<int32_t>((size_t)slices * Nq * k);
   // LDS: 2 ring stages + heaps [4][kh][32] keys (kh = k rounded up to 4 m + 1) + pending [4][pcap][64] keys, one column per LANE
   const int kh = 1 + ((k + 2) / 4) * 4;
-  const size_t fixed = (size_t)2 * 2 * TK_BQ * TK_BK * sizeof(float) + (size_t)4 * kh * 32 * 8 + TK_EU_LDS(EU);
+  const size_t fixed = (size_t)2 * 2 * TK_BQ * SLIC_RT_BK * sizeof(float) + (size_t)4 * kh * 32 * 8 + TK_EU_LDS(EU);
   int pcap = (int)((160 * 1024 - 16 - fixed) / (4 * 64 * 8));
   pcap = pcap > TK_PC_MAX ? TK_PC_MAX : pcap;
   SLIC_REQUIRE(pcap >= 2, "slic_cosine_topk: k = %d leaves no LDS for the pending buffers", k);
@@ -1330,7 +1228,7 @@ static int topk_collect(const TopkCollectPlan& c, const float* Qn, int Nq, const
   {
     const int kh = 1 + ((c.ms + 2) / 4) * 4;
     const int pcap = TK_PC_MAX;
-    const size_t lds = (size_t)2 * 2 * TK_BQ * TK_BK * sizeof(float) + (size_t)4 * kh * 32 * 8 + (size_t)4 * pcap * 64 * 8 + 16 + TK_EU_LDS(EU);
+    const size_t lds = (size_t)2 * 2 * TK_BQ * SLIC_RT_BK * sizeof(float) + (size_t)4 * kh * 32 * 8 + (size_t)4 * pcap * 64 * 8 + 16 + TK_EU_LDS(EU);
     dim3 grid((unsigned)slic_cdiv(Nq, TK_BQ), (unsigned)c.S1);
     const int ns = c.S1 * c.per1;
     const auto kern = D > 256 ? topk_partial_qreg<16, 4, EU> : D > 128 ? topk_partial_qreg<8, 4, EU> : topk_partial_qreg<4, 4, EU>;
@@ -1347,7 +1245,7 @@ static int topk_collect(const TopkCollectPlan& c, const float* Qn, int Nq, const
     per = (int)slic_cdiv(per, TK_BG) * TK_BG;
     const int S = (int)slic_cdiv(Ng, per);
     const int pcap = TK_PC_MAX;
-    const size_t lds = (size_t)4 * TK_BG * TK_BK * sizeof(float) + (size_t)4 * pcap * 64 * 8 + TK_EU_LDS(EU);
+    const size_t lds = (size_t)4 * TK_BG * SLIC_RT_BK * sizeof(float) + (size_t)4 * pcap * 64 * 8 + TK_EU_LDS(EU);
     dim3 grid((unsigned)slic_cdiv(Nq, TK_BQ), (unsigned)S);
     // scores tested per wave-wide branch: with ~0.4 % of the scores passing, SOME lane of the wave passes in most groups of four, so the
     // group maximum of the streaming kernels buys little here; SLIC_TOPK_GS = 1 / 2 / 4 selects (experiments; default below; the euclidean
