@@ -708,6 +708,35 @@ int slic_softmax_ce_bwd(const float* logits, int64_t ld, const float* lse, const
 int slic_dropout_fwd(const float* x, int64_t n, float p, uint64_t seed, uint64_t offset, float* y, void* stream);
 int slic_dropout_bwd(const float* dy, int64_t n, float p, uint64_t seed, uint64_t offset, float* dx, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * MoCo queue contrast (loss/NCE_loss.py MemoryMoCo :188-241; the InfoNCE / UberNCE loss of online_train.py:96-97): queries q [B, D]
+ * and keys k [B, D] against a dense queue memory [K, D], all row-major fp32, 1 <= D <= 512, K D < 2^29.
+ *   logit[b, 0] = <q_b, k_b> / T,  logit[b, 1 + j] = <memory_j, q_b> / T
+ * Exact fp32, no float atomics, fixed summation orders: the same inputs give the same bits.  There is no gradient to k or memory.
+ * The fused pair slic_moco_ce_fwd / _bwd holds no [B, K] and no [K, D] temporary.
+ * ---------------------------------------------------------------------------------------- */
+#define SLIC_MOCO_PARTS 256      /* most K-slices of a forward: slic_moco_ce_fwd's workspace is SLIC_MOCO_PARTS * B * 4 floats */
+#define SLIC_MOCO_DQ_PARTS 128   /* most K-slices of a backward: its workspace is SLIC_MOCO_DQ_PARTS * B * D floats */
+/* out [B, K + 1] = the logits */
+int slic_moco_logits_fwd(const float* q, const float* k, const float* memory, int B, int K, int D, float T, float* out,
+                         void* stream);
+/* dq [B, D] = (dout[:, 0] * k + dout[:, 1:] @ memory) / T; memory: the queue as it was scored */
+int slic_moco_logits_bwd(const float* dout, const float* k, const float* memory, int B, int K, int D, float T, float* dq,
+                         void* workspace, void* stream);
+/* loss = mean_b (lse_b - (sum of row b's positive logits) / npos_b).  Row b's positives: column 0 and, when k_label [B] and
+ * queue_label [K] (int64, -1 = empty slot; both or neither) are given, every j with queue_label[j] == k_label[b] >= 0.
+ * stat [4][B] = (logit[b, 0], lse_b, npos_b, row loss), kept for the backward.  workspace: 16-byte aligned. */
+int slic_moco_ce_fwd(const float* q, const float* k, const float* memory, int B, int K, int D, float T, const int64_t* k_label,
+                     const int64_t* queue_label, float* stat, float* loss, void* workspace, void* stream);
+/* dq [B, D] = (*gscale, NULL = 1) / (B T) * [ (p_b0 - w_b0) k_b + sum_j (p_bj - w_bj) memory_j ], p = softmax recomputed tile by tile
+ * from stat's lse, w = positives / npos; memory, the labels and stat as slic_moco_ce_fwd saw and left them */
+int slic_moco_ce_bwd(const float* q, const float* k, const float* memory, int B, int K, int D, float T, const int64_t* k_label,
+                     const int64_t* queue_label, const float* stat, const float* gscale, float* dq, void* workspace, void* stream);
+/* memory[(index + i) mod K] = k_i for i < B <= K (NCE_loss.py:233-239), queue_label[(index + i) mod K] = k_label[i] when
+ * queue_label is given */
+int slic_moco_enqueue(float* memory, int64_t* queue_label, const float* k, const int64_t* k_label, int B, int K, int D, int index,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -159,6 +159,12 @@ SIGNATURES = {
     "slic_softmax_ce_bwd": (I, [P, L, P, P, I, I, P, P, P]),
     "slic_dropout_fwd": (I, [P, L, F, ctypes.c_uint64, ctypes.c_uint64, P, P]),
     "slic_dropout_bwd": (I, [P, L, F, ctypes.c_uint64, ctypes.c_uint64, P, P]),
+    # MoCo queue contrast
+    "slic_moco_logits_fwd": (I, [P, P, P, I, I, I, F, P, P]),
+    "slic_moco_logits_bwd": (I, [P, P, P, I, I, I, F, P, P, P]),
+    "slic_moco_ce_fwd": (I, [P, P, P, I, I, I, F, P, P, P, P, P, P]),
+    "slic_moco_ce_bwd": (I, [P, P, P, I, I, I, F, P, P, P, P, P, P, P]),
+    "slic_moco_enqueue": (I, [P, P, P, P, I, I, I, I, P]),
 }
 
 

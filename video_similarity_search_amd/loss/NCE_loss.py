@@ -6,6 +6,11 @@ Drop-in for the memory-bank NCE of the reference's loss/NCE_loss.py:
 Same buffers (`params`, `memory_l`, `memory_ab`), same cross-wiring (out_ab is scored against memory_l, out_l
 against memory_ab), bank rows detached, momentum update + renormalise under no_grad.  The gather+bmm, its
 backward, the bank update and the class-0 cross-entropy are HIP kernels (csrc/nce.hip).
+    NCEAverage_intra_neg(inputSize, outputSize, K, T, momentum)(l, ab, neg, y, idx=None)       <- :91-184
+    MemoryMoCo(inputSize, outputSize, K, T, use_softmax)(q, k) -> out [B, K+1]                  <- :188-241
+MemoryMoCo scores a batch of queries against a dense queue (csrc/moco.hip): forward() returns the reference's output,
+softmax_loss() is the fused step (NCESoftmaxLoss on the logits, or the multi-positive UberNCE loss with labels) that never
+writes the [B, K+1] logits.
 The use_softmax=False branch (:54-71: out = exp(score / T / Z) with the constants Z_l / Z_ab fixed on the first call and
 kept in `params[2:4]`) and its NCECriterion (:312-337, Eq. 12 of the CMC paper) are not selected by SLIC
 (online_train.py:701-710 builds NCEAverage with the default and NCESoftmaxLoss); they are restated on top of the same
@@ -256,3 +261,228 @@ class NCECriterion(nn.Module):
         P_neg = x.narrow(1, 1, m)
         log_D0 = torch.div(P_neg.clone().fill_(m * Pn), P_neg.add(m * Pn + eps)).log_()
         return - (log_D1.sum(0) + log_D0.view(-1, 1).sum(0)) / bsz
+
+
+class NCEAverage_intra_neg(NCEAverage):
+    """NCEAverage with a third bank of intra-video negatives (loss/NCE_loss.py:91-184): each output scores the K+1 sampled rows of
+    the opposite bank followed by the same rows of `memory_neg` -> [B, 2(K+1), 1]; all three banks get the momentum update.
+    The same score / update kernels as NCEAverage, four score launches and three updates."""
+
+    def __init__(self, inputSize, outputSize, K, T=0.07, momentum=0.5, use_softmax=True):
+        if not torch.cuda.is_available():
+            raise _lib.SlicError("NCEAverage_intra_neg needs a gfx950 device (no CPU fallback)")
+        super(NCEAverage_intra_neg, self).__init__(inputSize, outputSize, K, T, momentum, use_softmax)
+        stdv = 1. / math.sqrt(inputSize / 3)
+        self.register_buffer('memory_neg', torch.rand(outputSize, inputSize).mul_(2 * stdv).add_(-stdv))
+
+    def forward(self, l, ab, neg, y, idx=None):
+        K, T, momentum = self._host_params()
+        batchSize = l.size(0)
+        if not l.is_cuda:
+            raise _lib.SlicError("NCEAverage_intra_neg needs device tensors (no CPU fallback)")
+        if idx is None:
+            idx = self.multinomial.draw(batchSize * (self.K + 1)).view(batchSize, -1)
+            idx.select(1, 0).copy_(y.data)
+        idx = idx.contiguous()
+        y = y.contiguous()
+        # :124-137: the bank's rows, then memory_neg's rows at the same indices
+        out_ab = torch.cat((_BankScores.apply(ab, self.memory_l, idx, T), _BankScores.apply(ab, self.memory_neg, idx, T)), 1)
+        out_l = torch.cat((_BankScores.apply(l, self.memory_ab, idx, T), _BankScores.apply(l, self.memory_neg, idx, T)), 1)
+        if not self.use_softmax:
+            # :145-159.  Unlike NCEAverage, Z comes from the mean of exp(score / T) and divides the exponential
+            outputSize = self.memory_l.size(0)
+            out_ab = torch.exp(out_ab)
+            out_l = torch.exp(out_l)
+            Z_l, Z_ab = self.params[2].item(), self.params[3].item()
+            if Z_l < 0:
+                self.params[2] = out_l.detach().mean() * outputSize
+                Z_l = self.params[2].item()
+                print("normalization constant Z_l is set to {:.1f}".format(Z_l))
+            if Z_ab < 0:
+                self.params[3] = out_ab.detach().mean() * outputSize
+                Z_ab = self.params[3].item()
+                print("normalization constant Z_ab is set to {:.1f}".format(Z_ab))
+            out_l = torch.div(out_l, Z_l).contiguous()
+            out_ab = torch.div(out_ab, Z_ab).contiguous()
+        with torch.no_grad():   # update memory (:161-182)
+            B, D = l.shape
+            for bank, f in ((self.memory_l, l), (self.memory_ab, ab), (self.memory_neg, neg)):
+                call("slic_nce_bank_update", ptr(bank), ptr(y), ptr(f.detach().contiguous().float()), B, D, float(momentum), stream())
+        return out_l, out_ab
+
+    def softmax_loss(self, *args, **kwargs):
+        raise NotImplementedError("the fused step is NCEAverage's; NCEAverage_intra_neg goes through forward()")
+
+
+_MOCO_PARTS, _MOCO_DQ_PARTS = 256, 128          # slic_hip.h: SLIC_MOCO_PARTS, SLIC_MOCO_DQ_PARTS
+
+
+class HipMoCoKernels:
+    """the device side of MemoryMoCo (csrc/moco.hip).  `MemoryMoCo(kernels=)` takes another provider with the same methods (tests of
+    the host logic on a GPU-less machine pass a NumPy one as an ARGUMENT; the product has no other)."""
+
+    def __init__(self):
+        _lib.load()
+
+    def check(self, *tensors):
+        for t in tensors:
+            if t is not None and not t.is_cuda:
+                raise _lib.SlicError("MemoryMoCo needs device tensors (no CPU fallback)")
+
+    def resident(self, t):
+        return t.contiguous().float()
+
+    def logits_fwd(self, q, k, memory, T):
+        (B, D), K = q.shape, memory.shape[0]
+        out = torch.empty(B, K + 1, dtype=torch.float32, device=q.device)
+        call("slic_moco_logits_fwd", ptr(q), ptr(k), ptr(memory), B, K, D, float(T), ptr(out), stream())
+        return out
+
+    def logits_bwd(self, dout, k, memory, T):
+        (B, D), K = k.shape, memory.shape[0]
+        dq = torch.empty(B, D, dtype=torch.float32, device=k.device)
+        ws = _lib.workspace(_MOCO_DQ_PARTS * B * D * 4, k.device, tag="moco")
+        call("slic_moco_logits_bwd", ptr(dout), ptr(k), ptr(memory), B, K, D, float(T), ptr(dq), ptr(ws), stream())
+        return dq
+
+    def ce_fwd(self, q, k, memory, T, k_label, queue_label):
+        """-> (loss, stat [4, B] = logit[:, 0], lse, npos, row loss)"""
+        (B, D), K = q.shape, memory.shape[0]
+        buf = torch.empty(4 * B + 1, dtype=torch.float32, device=q.device)
+        ws = _lib.workspace(_MOCO_PARTS * B * 16, q.device, tag="moco")
+        call("slic_moco_ce_fwd", ptr(q), ptr(k), ptr(memory), B, K, D, float(T), ptr(k_label), ptr(queue_label), ptr(buf),
+             ptr(buf[4 * B:]), ptr(ws), stream())
+        return buf[4 * B], buf[:4 * B].view(4, B)
+
+    def ce_bwd(self, q, k, memory, T, k_label, queue_label, stat):
+        """-> d loss / d q [B, D]; memory and the labels as ce_fwd saw them"""
+        (B, D), K = q.shape, memory.shape[0]
+        dq = torch.empty(B, D, dtype=torch.float32, device=q.device)
+        ws = _lib.workspace(_MOCO_DQ_PARTS * B * D * 4, q.device, tag="moco")
+        call("slic_moco_ce_bwd", ptr(q), ptr(k), ptr(memory), B, K, D, float(T), ptr(k_label), ptr(queue_label), ptr(stat), None,
+             ptr(dq), ptr(ws), stream())
+        return dq
+
+    def enqueue(self, memory, queue_label, k, k_label, index):
+        (B, D), K = k.shape, memory.shape[0]
+        call("slic_moco_enqueue", ptr(memory), ptr(queue_label), ptr(k), ptr(k_label), B, K, D, int(index), stream())
+
+
+class _MoCoLogits(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, k, memory, T, kern, keep):
+        out = kern.logits_fwd(kern.resident(q), k, memory, T)
+        ctx.T, ctx.kern = T, kern
+        if keep:
+            # forward() enqueues right after scoring: the backward gets the queue as it was scored (the reference clones it too, :214)
+            ctx.save_for_backward(k, memory.clone())
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        k, mem = ctx.saved_tensors
+        return ctx.kern.logits_bwd(ctx.kern.resident(g), k, mem, ctx.T), None, None, None, None, None
+
+
+class _MoCoFusedStep(torch.autograd.Function):
+    """the loss of a MoCo step as one autograd node.  The queue changes right after the forward, so d loss / d q is computed here,
+    against the queue as scored, and the backward only scales it: a later forward cannot reach into an earlier step's gradient."""
+
+    @staticmethod
+    def forward(ctx, q, k, memory, T, k_label, queue_label, kern, keep):
+        q = kern.resident(q)
+        loss, stat = kern.ce_fwd(q, k, memory, T, k_label, queue_label)
+        if keep:
+            ctx.save_for_backward(kern.ce_bwd(q, k, memory, T, k_label, queue_label, stat))
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        dq, = ctx.saved_tensors
+        return dq * g, None, None, None, None, None, None, None
+
+
+class MemoryMoCo(nn.Module):
+    """Fixed-size queue with momentum encoder (loss/NCE_loss.py:188-241).  forward(q, k) -> out [B, K+1] (also for B = 1, where the
+    reference's squeeze() drops the batch dimension), the batch of keys enqueued at `index` inside the call.
+    Extensions, keyword-only: labels=True adds the buffer `queue_label` [K] (int64, -1 = empty slot) for the multi-positive loss of
+    softmax_loss(q, k, k_label); kernels= takes another kernel provider (see HipMoCoKernels)."""
+
+    def __init__(self, inputSize, outputSize, K, T=0.07, use_softmax=False, *, labels=False, kernels=None):
+        super(MemoryMoCo, self).__init__()
+        self.outputSize = outputSize
+        self.inputSize = inputSize
+        self.queueSize = K
+        self.T = T
+        self.index = 0
+        self.use_softmax = use_softmax
+        self.labels = bool(labels)
+        self._kernels = kernels
+
+        self.register_buffer('params', torch.tensor([-1]))
+        stdv = 1. / math.sqrt(inputSize / 3)
+        self.register_buffer('memory', torch.rand(self.queueSize, inputSize).mul_(2 * stdv).add_(-stdv))
+        if self.labels:
+            self.register_buffer('queue_label', torch.full((self.queueSize,), -1, dtype=torch.long))
+        print('using queue shape: ({},{})'.format(self.queueSize, inputSize))
+
+    def _kern(self):
+        if self._kernels is None:
+            self._kernels = HipMoCoKernels()
+        return self._kernels
+
+    def _host_Z(self):
+        """params[0] as a Python number without a device round trip per step (see NCEAverage._host_params)"""
+        key = (self.params.data_ptr(), self.params._version)
+        if getattr(self, "_params_key", None) != key:
+            self._Z_host = self.params[0].item()
+            self._params_key = key
+        return self._Z_host
+
+    def _inputs(self, q, k, k_label):
+        if q.dim() != 2 or q.shape != k.shape or q.shape[1] != self.inputSize:
+            raise ValueError("MemoryMoCo expects q and k of shape [B, {}], got {} and {}".format(
+                self.inputSize, tuple(q.shape), tuple(k.shape)))
+        if q.shape[0] > self.queueSize:
+            raise ValueError("MemoryMoCo: a batch of {} keys does not fit a queue of {} rows (the reference's index_copy_ with "
+                             "repeated indices is undefined)".format(q.shape[0], self.queueSize))
+        if k_label is not None and not self.labels:
+            raise ValueError("MemoryMoCo: k_label needs a module built with labels=True")
+        kern = self._kern()
+        kern.check(q, k, k_label, self.memory)
+        k = kern.resident(k.detach())
+        if self.labels:
+            # a step without labels leaves empty slots behind, never stale labels
+            k_label = (torch.full((q.shape[0],), -1, dtype=torch.long, device=q.device) if k_label is None
+                       else k_label.detach().contiguous().long())
+        return kern, k, k_label
+
+    def _enqueue(self, kern, k, k_label):
+        with torch.no_grad():   # update memory (:233-239)
+            kern.enqueue(self.memory, self.queue_label if self.labels else None, k, k_label, self.index)
+            self.index = (self.index + k.shape[0]) % self.queueSize
+
+    def forward(self, q, k):
+        kern, k, k_label = self._inputs(q, k, None)
+        out = _MoCoLogits.apply(q, k, self.memory, self.T, kern, torch.is_grad_enabled() and q.requires_grad)
+        if not self.use_softmax:
+            out = torch.exp(out)
+            if self._host_Z() < 0:
+                self.params[0] = out.detach().mean() * self.outputSize
+                print("normalization constant Z is set to {:.1f}".format(self._host_Z()))
+            out = torch.div(out, self._host_Z()).contiguous()
+        self._enqueue(kern, k, k_label)
+        return out
+
+    def softmax_loss(self, q, k, k_label=None):
+        """== NCESoftmaxLoss()(self(q, k)) with the same queue update, without the [B, K+1] logits.  With k_label [B] (labels=True):
+        row b's positives are column 0 and every queue row of its label; loss = mean_b -(sum_pos log_softmax) / n_pos
+        (online_train.py:96-97 on the mask of models/infoNCE.py:281-283), and the labels are enqueued with the keys."""
+        if not self.use_softmax:
+            raise NotImplementedError("softmax_loss is the use_softmax=True step; the exp / Z outputs go through forward()")
+        multi = k_label is not None
+        kern, k, k_label = self._inputs(q, k, k_label)
+        loss = _MoCoFusedStep.apply(q, k, self.memory, self.T, k_label if multi else None, self.queue_label if multi else None, kern,
+                                    torch.is_grad_enabled() and q.requires_grad)
+        self._enqueue(kern, k, k_label)
+        return loss
