@@ -607,6 +607,38 @@ int slic_dbscan_cosine(const float* X, int64_t N, int ldx, int D, double eps, in
 int slic_dbscan_cosine_stats(const void* workspace, double* out_host /* [10] */, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Average-linkage agglomerative clustering, cosine metric, cut by a distance threshold (clustering/cluster_masks.py:49-54 ->
+ * sklearn.cluster.AgglomerativeClustering(n_clusters=None, linkage='average', distance_threshold=t, affinity='cosine')).
+ * The rows are L2-normalised (slic_normalize_rows) and zero-padded to Dp = D rounded up to 8.  A cluster is the sum S of its unit rows and
+ * their number n; d(A, B) = clip(1 - (S_A / n_A) . (S_B / n_B), 0, 2) in fp32, as slic_cosine_topk computes it on the means: the average
+ * of all pairwise cosine distances between A and B.  State lives in the caller's workspace between the calls:
+ *   slic_agglo_start          every row a live, "stale" cluster.  *bad_rows_host = rows of zero norm or with a non-finite value: an argument
+ *                             error the caller reports (nothing else may be called on that workspace then).  Synchronises the stream.
+ *   slic_agglo_round          A = live clusters, Q = stale live clusters (the host knows both: N, N after the start, then the record's).
+ *                             Every stale cluster searches the A means for its nearest OTHER cluster nn (ties -> lower id) at distance nd;
+ *                             every pair a < b with nn[a] == b, nn[b] == a and nd[a] < threshold merges: S[a] += S[b], n[a] += n[b], b dies,
+ *                             parent[b] = a.  Then a live cluster is stale when it merged or its nn merged or died (average linkage is
+ *                             reducible: any other cached nn is still a nearest cluster).  record_host (SLIC_AGGLO_RECORD int64):
+ *                             [0] pairs merged, [1] live clusters, [2] stale clusters after the round, [3] (bits of nd << 32) | id of the
+ *                             live cluster with the smallest (nd, id) at the start of the merge step, [4] nanoseconds the search took on
+ *                             the device when SLIC_AGGLO_TIMING=1 was set at the call (else -1; measurement only).  One device-to-host
+ *                             copy and one synchronisation per round.  topk_workspace: slic_cosine_topk_workspace_bytes(Q, A, 2) bytes.
+ *   slic_agglo_merge_closest  after a round that merged nothing: merges the record's closest cluster [3] with its nn (the lower id
+ *                             survives) and marks stale as a round does; record_host [0] = 1 (0 if there was no such pair), [1], [2] as above.
+ *   slic_agglo_labels         labels[i] (device, int32 [N]) = the rank of i's cluster among the live clusters in ascending order of their
+ *                             smallest member: 0 .. C-1 in order of first appearance.  The state is left usable.
+ * No floating-point atomics: one wave owns a merging pair and every lane its own columns, so two runs give the same bits.
+ * Limits: 1 <= N <= SLIC_AGGLO_MAX_N, 1 <= D <= 512, N * Dp * 4 < 4 GiB; SLIC_EINVAL beyond.  The workspace is 3 N Dp floats + O(N). */
+#define SLIC_AGGLO_MAX_N ((int64_t)1 << 24)
+#define SLIC_AGGLO_RECORD 5
+size_t slic_agglo_workspace_bytes(int64_t N, int D);               /* 0 for sizes slic_agglo_start rejects */
+int slic_agglo_start(const float* X, int64_t N, int ldx, int D, void* workspace, int32_t* bad_rows_host, void* stream);
+int slic_agglo_round(void* workspace, int64_t N, int D, int A, int Q, float threshold, void* topk_workspace, int64_t* record_host,
+                     void* stream);
+int slic_agglo_merge_closest(void* workspace, int64_t N, int D, int64_t* record_host, void* stream);
+int slic_agglo_labels(void* workspace, int64_t N, int D, int32_t* labels, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Cluster-quality metrics of the cluster step (online_train.py:633-639 -> sklearn.metrics.normalized_mutual_info_score and
  * adjusted_mutual_info_score, both with average_method='arithmetic'): one call, one fp64 record.  The rules are sklearn 1.7.2's
  * (sklearn/metrics/cluster/_supervised.py:819-924, :1022-1062, :1146-1174, :1281-1314, _expected_mutual_info_fast.pyx):

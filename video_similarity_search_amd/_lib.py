@@ -142,6 +142,12 @@ SIGNATURES = {
     "slic_dbscan_cosine_workspace_bytes": (c_size_t, [L, I]),
     "slic_dbscan_cosine": (I, [P, L, I, I, Dbl, I, P, P, P, P, P, P]),
     "slic_dbscan_cosine_stats": (I, [P, P, P]),
+    # average-linkage agglomerative clustering (cosine, distance threshold)
+    "slic_agglo_workspace_bytes": (c_size_t, [L, I]),
+    "slic_agglo_start": (I, [P, L, I, I, P, P, P]),
+    "slic_agglo_round": (I, [P, L, I, I, I, F, P, P, P]),
+    "slic_agglo_merge_closest": (I, [P, L, I, P, P]),
+    "slic_agglo_labels": (I, [P, L, I, P, P]),
     # cluster-quality metrics (NMI / AMI)
     "slic_cluster_metrics_workspace_bytes": (c_size_t, [L, L]),
     "slic_cluster_metrics": (I, [P, P, L, L, P, P, P]),

@@ -4,8 +4,9 @@ Drop-in for the reference's clustering/cluster_masks.py on the k-means path:
     fit_cluster(embeddings, method, k, l2normalize, finch_partition)   <- cluster_masks.py:38-98
 Same names, argument meaning, prints and return type (np.ndarray[N] labels).  method='kmeans'
 (SURVEY.md §8 A5/A6), method='finch' (§8f row 1: the method the shipped configs select) and
-method='DBSCAN' (cosine, clustering/dbscan.py) run on the GPU; 'Agglomerative' and 'OPTICS', which the
-reference dispatches to sklearn on the host, raise.
+method='DBSCAN' (cosine, clustering/dbscan.py) run on the GPU, and so does method='Agglomerative' (average linkage, cosine,
+clustering/agglomerative.py) once the caller states its distance_threshold; 'OPTICS', which the reference dispatches to sklearn
+on the host, raises.
 """
 import numpy as np
 import torch
@@ -43,11 +44,15 @@ def preprocess_features_kmeans(data, kernels=None):
 
 def fit_cluster(embeddings, method='Agglomerative', k=1000, l2normalize=True, finch_partition=0,
                 n_init=10, init='k-means++', process_group=None, random_state=None, kernels=None, exchange=None,
-                *, eps=0.14, min_samples=2):
+                *, eps=0.14, min_samples=2, distance_threshold=None):
     """Reference signature + keyword-only extras (n_init / init / process_group / random_state / kernels / exchange / eps /
     min_samples) that default to the reference's behaviour: KMeans(n_clusters=k, n_init=10).fit(embeddings).labels_, and for
     method='DBSCAN' DBSCAN(eps=0.14, min_samples=2, metric='cosine').fit(embeddings).labels_ (noise = -1; l2normalize does not
     apply, as in the reference; `kernels` is then a DBSCAN provider, see clustering/dbscan.py).
+    method='Agglomerative' with distance_threshold=t runs AgglomerativeClustering(n_clusters=None, linkage='average',
+    distance_threshold=t, metric='cosine').fit(embeddings).labels_ (clustering/agglomerative.py: sklearn's partition, clusters numbered
+    by their smallest row; `kernels` is then an agglomerative provider).  The reference's t is the hand-tuned constant 0.24 ("0.24 for
+    ucf train", cluster_masks.py:52): the caller states it; without it the method raises NotImplementedError.
     process_group: `embeddings` is this rank's row shard (rank order == row order), the returned labels are this rank's.
     exchange: the sharded Lloyd iteration's one collective — 'allreduce' (RCCL through torch.distributed; the default), 'allgather', or
     'oneshot' (the library's one-shot all-to-all over peer-mapped memory, csrc/oneshot.hip); None reads SLIC_KMEANS_EXCHANGE."""
@@ -68,10 +73,16 @@ def fit_cluster(embeddings, method='Agglomerative', k=1000, l2normalize=True, fi
         # cluster_masks.py:55-61: DBSCAN(eps=0.14, min_samples=2, metric='cosine', n_jobs=-1).fit(embeddings)
         from .dbscan import DBSCAN
         km = DBSCAN(eps=eps, min_samples=min_samples, metric='cosine', kernels=kernels).fit(embeddings)
+    elif method == 'Agglomerative' and distance_threshold is not None:
+        # cluster_masks.py:49-54: AgglomerativeClustering(n_clusters=None, linkage='average', distance_threshold=0.24, affinity='cosine')
+        from .agglomerative import AgglomerativeClustering
+        km = AgglomerativeClustering(n_clusters=None, linkage='average', distance_threshold=distance_threshold, metric='cosine',
+                                     kernels=kernels).fit(embeddings)
     elif method not in ('kmeans', 'spherical_kmeans'):
         raise NotImplementedError(
-            f"method={method!r}: 'kmeans', 'spherical_kmeans', 'finch' and 'DBSCAN' are on the MI355X hot path; average-linkage "
-            "agglomerative clustering and OPTICS are sequential algorithms the reference runs on the host through sklearn")
+            f"method={method!r}: 'kmeans', 'spherical_kmeans', 'finch' and 'DBSCAN' are on the MI355X hot path, and so is 'Agglomerative' "
+            "when the keyword distance_threshold= is given (the reference's hand-tuned 0.24 is not assumed); OPTICS is a sequential "
+            "algorithm the reference runs on the host through sklearn")
     elif method == 'spherical_kmeans':
         x = _to_device(embeddings) if kernels is None else kernels.to_device(embeddings)
         # cluster_masks.py:73-77: SphericalKMeans(n_clusters=k).fit(embeddings) (spherecluster: normalises the rows itself,
