@@ -12,6 +12,7 @@
 // Build: -ffp-contract=off (nothing fuses except explicit fmaf/MFMA).
 #include "mfma_ring.h"
 #include <type_traits>
+#include <utility>
 #include <math.h>
 #include <stdlib.h>
 
@@ -1337,7 +1338,6 @@ __global__ void cs_search(const float* __restrict__ v, int64_t N, const double* 
       run += pl;
     }
     // the crossing lane: first lane whose inclusive prefix reaches x
-    const bool crosses = (mine + part >= x) && (mine < x || lane == 0);
     const unsigned long long m = __ballot(mine + part >= x);
     const int first = m ? __ffsll((long long)m) - 1 : -1;
     int64_t r = -1;
@@ -1350,7 +1350,6 @@ __global__ void cs_search(const float* __restrict__ v, int64_t N, const double* 
         if (a >= x) { r = s0 + u; break; }
       }
     }
-    (void)crosses;
     if (first >= 0) res = __shfl(r, first);
     else res = (lo + 1) * 1024 < N ? (lo + 1) * 1024 : N;
   }
@@ -1359,10 +1358,12 @@ __global__ void cs_search(const float* __restrict__ v, int64_t N, const double* 
 }
 
 // ---------------- k-means++ as one device-driven sequence (no host round trip per centre) ----------------------
-// Step c: (1) kpp_search: T candidates = searchsorted(cumsum(closest), u[c] * current_pot)  (2) kpp_dist_rows: squared
-// distances of every row to the T candidates, min with closest, per-256-row potentials  (3) kpp_select: potentials,
-// first-minimum candidate, its index into idx[c], and the inclusive scan of ITS per-256-row sums = the chunked cumsum
-// step c+1 searches.  `closest` is never copied: it is row `sel` of the previous step's newdist buffer (double-buffered).
+// Step c of a run: (1) a distance kernel (kpp_dist_mfma on the matrix pipe, or kpp_dist_rows on the VALU when the caller has
+// no k-permuted copy): squared distances of every row to the run's T candidates, min with closest, potentials per KPP_CH = 64 rows
+// (2) kpp_select: potentials, first-minimum candidate, its index into idx[c], the inclusive scan of ITS chunk sums = the chunked
+// cumsum, and on that cumsum the draw of step c+1's T candidates = searchsorted(cumsum(closest), u[c] * potential)  (kpp_search).
+// `closest` is never copied: it is row `sel` of the previous step's newdist buffer (double-buffered).
+// The R initialisations of KMeans(n_init = R) take every step together (R = 1 is a single run): see kpp_dist_mfma.
 
 // one wave per row: the row is read as one contiguous run (16 B per lane), candidate rows sit in LDS.  A workgroup covers
 // KPP_CH = 64 rows (16 per wave, two rows in flight per wave): ~1600 workgroups at N = 100k, enough waves to hide the
@@ -1454,224 +1455,22 @@ __global__ __launch_bounds__(256) void kpp_dist_rows(const float* __restrict__ X
   }
 }
 
-// The same distances on the matrix pipe: d(x, c) = |x|^2 + |c|^2 - 2 x.c  (sklearn's own formulation,
-// euclidean_distances with precomputed row norms), x.c by v_mfma_f32_32x32x2_f32 with A = the T (<= 16) candidate rows
-// padded to one 32-row tile and B = 128 points per workgroup, both DMA'd from the k-permuted copy of X (the candidates ARE
-// rows of it) through the 2-stage LDS ring of the E-step.  One pass over X per centre at HBM speed instead of a VALU loop.
-// A workgroup covers two KPP_CH = 64 row chunks (waves 0-1, waves 2-3).
+// ---- the matrix-pipe distances, for the R initialisations of KMeans(n_init = R) side by side (R = 1: a single run) ----------------------
+// d(x, c) = |x|^2 + |c|^2 - 2 x.c  (sklearn's own formulation, euclidean_distances with precomputed row norms), x.c by
+// v_mfma_f32_32x32x2_f32 with A = candidate rows in tiles of 32 and B = 128 points per workgroup, both DMA'd from the k-permuted copy of
+// X (the candidates ARE rows of it) through a 2-stage LDS ring.  One pass over X per centre at HBM speed instead of a VALU loop.  A
+// workgroup covers two KPP_CH = 64 row chunks (waves 0-1, waves 2-3).
+// sklearn runs the R initialisations one after the other, but the only thing they share is the RNG stream, and k-means++'s draws do not
+// depend on the data: with the uniforms drawn up front (in the order the sequential loop draws them) the R runs are independent.  Step c
+// of ALL of them is then ONE pass over X — R x T candidate rows as NG tiles of 32 MFMA rows per workgroup instead of one pass per run
+// (a pass is HBM-bound at T = 8 rows: 46 us per centre) — and one selection launch of R workgroups.  Row q = r * T + t of the candidate
+// matrix belongs to run r; every run keeps its own closest-distance arrays, potentials, chunk sums and picks, and nothing in its
+// arithmetic or its order depends on R: run r of R computes what a launch with R = 1 computes, bit for bit.
+template <int NG>
 __global__ __launch_bounds__(256) void kpp_dist_mfma(const float* __restrict__ Xp, const float* __restrict__ xnorm, int64_t N,
-                                                     int D, int ldx, const int32_t* __restrict__ cand, int T,
+                                                     int D, int ldx, const int32_t* __restrict__ cand, int RT, int T, int Tprev,
                                                      const float* __restrict__ prev, const int32_t* __restrict__ sel,
                                                      float* __restrict__ newdist, double* __restrict__ bpart, int64_t nchunk) {
-  extern __shared__ __attribute__((aligned(16))) float km_lds[];
-  constexpr int BP = 128;
-  constexpr int STAGE_FLOATS = (BP + 32) * SLIC_RT_BK;
-  __shared__ float cn[PP_TMAX];
-  __shared__ double wp[4][PP_TMAX];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int64_t pblock = (int64_t)blockIdx.x * BP;
-  const int srow = tid >> 3;
-  const int cq = (tid & 7) ^ ((srow >> 1) & 7);
-  const int64_t xrows = (N - pblock) < BP ? (N - pblock) : BP;
-  const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)(Xp + pblock * (int64_t)ldx), 0, (int)(((xrows - 1) * (int64_t)ldx + D) * 4), 0x00020000);
-  const __amdgpu_buffer_rsrc_t rs_c = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)Xp, 0, (int)(((N - 1) * (int64_t)ldx + D) * 4), 0x00020000);
-  constexpr unsigned OOB = 0xFFFFFF00u;
-  unsigned xoff[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) xoff[i] = (srow + 32 * i) < xrows ? ((unsigned)(srow + 32 * i) * (unsigned)ldx + cq * 4) * 4u : OOB;
-  const unsigned coff = srow < T ? ((unsigned)cand[srow] * (unsigned)ldx + cq * 4) * 4u : OOB;     // candidate row `srow`
-  if (tid < T) cn[tid] = xnorm[cand[tid]];
-  const int klim = D - cq * 4;
-  const int nk = (D + SLIC_RT_BK - 1) / SLIC_RT_BK;
-  auto issue = [&](int kt, int stage) {
-    float* Xs = km_lds + stage * STAGE_FLOATS;
-    float* Cs = Xs + BP * SLIC_RT_BK;
-    const bool kin = kt * SLIC_RT_BK < klim;
-    const unsigned kb = (unsigned)kt * (SLIC_RT_BK * 4u);
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_x, (__attribute__((address_space(3))) void*)(Xs + (8 * wave + 32 * i) * SLIC_RT_BK),
-                                               16, (int)((kin && xoff[i] != OOB) ? xoff[i] + kb : OOB), 0, 0, 0);
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_c, (__attribute__((address_space(3))) void*)(Cs + (8 * wave) * SLIC_RT_BK),
-                                             16, (int)((kin && coff != OOB) ? coff + kb : OOB), 0, 0, 0);
-  };
-  f32x16 acc;
-#pragma unroll
-  for (int v = 0; v < 16; ++v) acc[v] = 0.f;
-  const int r = lane & 31, h = lane >> 5;
-  constexpr int PER_STAGE = 5;
-  issue(0, 0);
-  for (int s0 = 0; s0 < nk; s0 += 2) {
-#pragma unroll
-    for (int sidx = 0; sidx < 2; ++sidx) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-      issue(s0 + sidx + 1, sidx ^ 1);
-      const float* Xs = km_lds + sidx * STAGE_FLOATS;
-      const float* Cs = Xs + BP * SLIC_RT_BK;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const f32x4 b = *(const f32x4*)&Xs[slic_rt_off(32 * wave + r, 2 * q + h)];
-        const f32x4 a = *(const f32x4*)&Cs[slic_rt_off(r, 2 * q + h)];
-#pragma unroll
-        for (int t = 0; t < 4; ++t) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[t], b[t], acc, 0, 0, 0);
-      }
-    }
-  }
-  (void)PER_STAGE;
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  const float* closest = prev ? prev + (int64_t)(*sel) * N : nullptr;
-  const int64_t i = pblock + 32 * wave + r;
-  const bool iv = i < N;
-  const float xn = iv ? xnorm[i] : 0.f;
-  const float cl = (closest && iv) ? closest[i] : INFINITY;
-#pragma unroll
-  for (int g = 0; g < 16; ++g) {
-    const int t = (g & 3) + 8 * (g >> 2) + 4 * h;           // candidate row held in accumulator register g of this lane half
-    if (t < T) {                                             // uniform per (g, h)
-      const float d = fmaxf(xn + cn[t] - 2.0f * acc[g], 0.f);
-      const float m = fminf(d, cl);
-      if (iv) newdist[(int64_t)t * N + i] = m;
-      double v = iv ? (double)m : 0.0;
-      for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o);     // over the 32 points of this wave (lane half keeps its t)
-      if (r == 0) wp[wave][t] = v;
-    }
-  }
-  __syncthreads();
-  if (tid < T) {
-    const int64_t c0 = (int64_t)blockIdx.x * 2;
-    bpart[c0 * T + tid] = wp[0][tid] + wp[1][tid];
-    if (c0 + 1 < nchunk) bpart[(c0 + 1) * T + tid] = wp[2][tid] + wp[3][tid];
-  }
-}
-
-// one workgroup of 16 waves: pot[t] = sum_b bpart[b][t] — wave t sums candidate t's column (lanes strided over the chunks,
-// then a fixed shuffle tree) — sel = first minimum, idx_out = cand[sel], csum[b] = inclusive scan over b of bpart[b][sel]
-// (per-thread runs, wave shuffle scans, one scan of the 16 wave totals).  Latency-bound: a handful of barriers in all.
-#define KPP_ST 1024
-// The draw of the NEXT step's candidates (kpp_search's arithmetic, wave t = candidate t) follows in the same launch when
-// u_next is given: it needs nothing but this launch's csum / sel / potential, and a separate 7 us launch per centre is a
-// tenth of a k-means++ run.  csum and cand are deliberately not __restrict__/const here: they are written and re-read.
-__global__ __launch_bounds__(KPP_ST) void kpp_select(const double* __restrict__ bpart, int64_t nblk, int T,
-                                                     int32_t* cand, int32_t* __restrict__ sel,
-                                                     double* __restrict__ cur_pot, double* csum,
-                                                     int32_t* __restrict__ idx_out, const float* __restrict__ nd_cur, int64_t N,
-                                                     const double* __restrict__ u_next, int Tn) {
-  __shared__ double pots[PP_TMAX];
-  __shared__ double wtot[KPP_ST / 64];
-  __shared__ int s_sel;
-  const int i = threadIdx.x, lane = i & 63, wave = i >> 6;
-  if (wave < T) {
-    double a = 0.0;
-    for (int64_t b = lane; b < nblk; b += 64) a += bpart[b * T + wave];
-    for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o);
-    if (lane == 0) pots[wave] = a;
-  }
-  __syncthreads();
-  if (i == 0) {
-    int b = 0;
-    for (int t = 1; t < T; ++t) if (pots[t] < pots[b]) b = t;          // np.argmin: first minimum
-    s_sel = b;
-    *sel = b;
-    *cur_pot = pots[b];
-    *idx_out = cand[b];
-  }
-  __syncthreads();
-  const int b = s_sel;
-  // inclusive scan of column b: thread i owns the run of `per` consecutive chunks [i * per, ...)
-  const int64_t per = (nblk + KPP_ST - 1) / KPP_ST;
-  const int64_t c0 = (int64_t)i * per, c1 = c0 + per < nblk ? c0 + per : nblk;
-  double run = 0.0;
-  for (int64_t c = c0; c < c1; ++c) run += bpart[c * T + b];
-  double inc = run;                                                     // inclusive scan of the run totals inside the wave
-  for (int d = 1; d < 64; d <<= 1) {
-    const double u = __shfl_up(inc, d);
-    if (lane >= d) inc += u;
-  }
-  if (lane == 63) wtot[wave] = inc;
-  __syncthreads();
-  double woff = 0.0;
-  for (int w = 0; w < wave; ++w) woff += wtot[w];                       // <= 15 adds, same order in every thread of the wave
-  double a = woff + inc - run;                                          // exclusive offset of this thread's run
-  for (int64_t c = c0; c < c1; ++c) { a += bpart[c * T + b]; csum[c] = a; }
-  if (!u_next) return;
-  __syncthreads();                                                       // csum is complete (and visible: one workgroup)
-  static_assert(KPP_CH == 64 && KPP_ST / 64 >= PP_TMAX, "one wave per candidate, one element per lane");
-  if (wave >= Tn) return;
-  // x = u * potential; searchsorted(cumsum(v), x, 'left') with the cumsum taken in KPP_CH-element chunks — kpp_search, verbatim
-  const float* v = nd_cur + (int64_t)b * N;
-  const double x = u_next[wave] * pots[b];
-  int64_t lo = 0, hi = nblk;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (csum[mid] < x) lo = mid + 1; else hi = mid;
-  }
-  int64_t res = N;
-  if (lo < nblk) {
-    const double base = lo ? csum[lo - 1] : 0.0;
-    const int64_t e = lo * KPP_CH + lane;
-    const double part = e < N ? (double)v[e] : 0.0;
-    double runs = base, incl = 0.0;
-    for (int l = 0; l < 64; ++l) {                       // sequential inclusive scan in lane order
-      runs += __shfl(part, l);
-      if (l == lane) incl = runs;
-    }
-    const unsigned long long m = __ballot(incl >= x && e < N);
-    res = m ? lo * KPP_CH + (__ffsll((long long)m) - 1) : ((lo + 1) * KPP_CH < N ? (lo + 1) * KPP_CH : N);
-  }
-  if (res > N - 1) res = N - 1;
-  if (lane == 0) cand[wave] = (int32_t)res;
-}
-
-// one WAVE per query: x = u * (*cur_pot); searchsorted(cumsum(v), x, 'left') with the cumsum taken in KPP_CH-element
-// chunks (inclusive chunk sums csum, one element per lane inside the chunk) in double, clipped to N - 1
-__global__ void kpp_search(const float* __restrict__ prev, const int32_t* __restrict__ sel, int64_t N,
-                           const double* __restrict__ csum, int64_t nchunk, const double* __restrict__ u,
-                           const double* __restrict__ cur_pot, int T, int32_t* __restrict__ idx) {
-  static_assert(KPP_CH == 64, "one element per lane");
-  const int t = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  if (t >= T) return;
-  const float* v = prev + (int64_t)(*sel) * N;
-  const int lane = threadIdx.x & 63;
-  const double x = u[t] * (*cur_pot);
-  int64_t lo = 0, hi = nchunk;  // first chunk whose inclusive sum >= x
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (csum[mid] < x) lo = mid + 1; else hi = mid;
-  }
-  int64_t res = N;
-  if (lo < nchunk) {
-    const double base = lo ? csum[lo - 1] : 0.0;
-    const int64_t e = lo * KPP_CH + lane;
-    const double part = e < N ? (double)v[e] : 0.0;
-    double run = base, incl = 0.0;
-    for (int l = 0; l < 64; ++l) {                       // sequential inclusive scan in lane order
-      run += __shfl(part, l);
-      if (l == lane) incl = run;
-    }
-    const unsigned long long m = __ballot(incl >= x && e < N);
-    res = m ? lo * KPP_CH + (__ffsll((long long)m) - 1) : ((lo + 1) * KPP_CH < N ? (lo + 1) * KPP_CH : N);
-  }
-  if (res > N - 1) res = N - 1;
-  if (lane == 0) idx[t] = (int32_t)res;
-}
-
-// ---- the R initialisations of KMeans(n_init = R) side by side ---------------------------------------------------------------
-// sklearn runs them one after the other, but the only thing they share is the RNG stream, and k-means++'s draws do not depend on
-// the data: with the uniforms drawn up front (in the order the sequential loop draws them) the R runs are independent.  Step c of
-// ALL of them is then ONE pass over X — R x T candidate rows as NG tiles of 32 MFMA rows per workgroup instead of one pass per
-// run (the single-run pass is HBM-bound at T = 8 rows: 46 us per centre and run) — and one selection launch of R workgroups.
-// Row q = r * T + t of the candidate matrix belongs to run r; every run keeps its own closest-distance arrays, potentials,
-// chunk sums and picks, with exactly the arithmetic (and order) of the single-run kernels above: the results are bit-identical.
-template <int NG>
-__global__ __launch_bounds__(256) void kpp_dist_mfma_batch(const float* __restrict__ Xp, const float* __restrict__ xnorm, int64_t N,
-                                                           int D, int ldx, const int32_t* __restrict__ cand, int RT, int T, int Tprev,
-                                                           const float* __restrict__ prev, const int32_t* __restrict__ sel,
-                                                           float* __restrict__ newdist, double* __restrict__ bpart, int64_t nchunk) {
   extern __shared__ __attribute__((aligned(16))) float km_lds[];
   constexpr int BP = 128, CR = 32 * NG;
   constexpr int STAGE_FLOATS = (BP + CR) * SLIC_RT_BK;
@@ -1742,6 +1541,8 @@ __global__ __launch_bounds__(256) void kpp_dist_mfma_batch(const float* __restri
   const int64_t i = pblock + 32 * wave + r;
   const bool iv = i < N;
   const float xn = iv ? xnorm[i] : 0.f;
+  const bool one = NG == 1 && RT == T;                            // a single run: every candidate row has the same closest, loaded once per lane
+  const float cl1 = (one && prev && iv) ? prev[(int64_t)sel[0] * N + i] : INFINITY;
 #pragma unroll
   for (int g = 0; g < NG; ++g)
 #pragma unroll
@@ -1749,7 +1550,7 @@ __global__ __launch_bounds__(256) void kpp_dist_mfma_batch(const float* __restri
       const int q = 32 * g + (e & 3) + 8 * (e >> 2) + 4 * h;      // candidate row held in accumulator element e of this lane half
       if (q < RT) {                                               // uniform per (g, e, h)
         const int run = q / T;
-        const float cl = (prev && iv) ? prev[((int64_t)run * Tprev + sel[run]) * N + i] : INFINITY;
+        const float cl = one ? cl1 : (prev && iv) ? prev[((int64_t)run * Tprev + sel[run]) * N + i] : INFINITY;
         const float d = fmaxf(xn + cn[q] - 2.0f * acc[g][e], 0.f);
         const float m = fminf(d, cl);
         if (iv) newdist[(int64_t)q * N + i] = m;
@@ -1766,24 +1567,57 @@ __global__ __launch_bounds__(256) void kpp_dist_mfma_batch(const float* __restri
   }
 }
 
-// kpp_select for run r = blockIdx.x: its T columns of bpart (row stride RT), its sel / potential / chunk sums / candidates / picks
-__global__ __launch_bounds__(KPP_ST) void kpp_select_batch(const double* __restrict__ bpart_all, int64_t nblk, int T, int RT, int Tn,
-                                                           const int32_t* __restrict__ cand_all, int32_t* __restrict__ cand_next_all,
-                                                           int32_t* __restrict__ sel_all,
-                                                           double* __restrict__ pot_all, double* csum_all,
-                                                           int32_t* __restrict__ idx_out_all, int idx_stride,
-                                                           const float* __restrict__ nd_cur_all, int64_t N,
-                                                           const double* __restrict__ u_next_all, int64_t u_stride) {
+// one WAVE per query x: searchsorted(cumsum(v), x, 'left') clipped to N - 1, with the cumsum taken in double in KPP_CH-element chunks:
+// binary search for the first chunk whose inclusive sum csum reaches x, then one element per lane inside that chunk
+__device__ __forceinline__ int32_t kpp_search(const float* v, int64_t N, const double* csum, int64_t nchunk, double x, int lane) {
+  static_assert(KPP_CH == 64, "one element per lane");
+  int64_t lo = 0, hi = nchunk;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (csum[mid] < x) lo = mid + 1; else hi = mid;
+  }
+  int64_t res = N;
+  if (lo < nchunk) {
+    const double base = lo ? csum[lo - 1] : 0.0;
+    const int64_t e = lo * KPP_CH + lane;
+    const double part = e < N ? (double)v[e] : 0.0;
+    double runs = base, incl = 0.0;
+    for (int l = 0; l < 64; ++l) {                       // sequential inclusive scan in lane order
+      runs += __shfl(part, l);
+      if (l == lane) incl = runs;
+    }
+    const unsigned long long m = __ballot(incl >= x && e < N);
+    res = m ? lo * KPP_CH + (__ffsll((long long)m) - 1) : ((lo + 1) * KPP_CH < N ? (lo + 1) * KPP_CH : N);
+  }
+  if (res > N - 1) res = N - 1;
+  return (int32_t)res;
+}
+
+// one workgroup of 16 waves per run (run r = blockIdx.x: its T columns of bpart, row stride RT, its sel / potential / chunk sums /
+// candidates / picks): pot[t] = sum_b bpart[b][t] — wave t sums candidate t's column (lanes strided over the chunks, then a fixed shuffle
+// tree) — sel = first minimum, idx_out = cand[sel], csum[b] = inclusive scan over b of bpart[b][sel] (per-thread runs, wave shuffle
+// scans, one scan of the 16 wave totals).  Latency-bound: a handful of barriers in all.
+// The draw of the NEXT step's candidates (wave t = candidate t) follows in the same launch when u_next is given: it needs nothing but
+// this launch's csum / sel / potential, and a separate 7 us launch per centre is a tenth of a k-means++ run.  csum is deliberately not
+// __restrict__/const: it is written and re-read.  The next candidates go to the other buffer: the runs' workgroups are concurrent.
+#define KPP_ST 1024
+__global__ __launch_bounds__(KPP_ST) void kpp_select(const double* __restrict__ bpart_all, int64_t nblk, int T, int RT, int Tn,
+                                                     const int32_t* __restrict__ cand_all, int32_t* __restrict__ cand_next_all,
+                                                     int32_t* __restrict__ sel_all,
+                                                     double* __restrict__ pot_all, double* csum_all,
+                                                     int32_t* __restrict__ idx_out_all, int idx_stride,
+                                                     const float* __restrict__ nd_cur_all, int64_t N,
+                                                     const double* __restrict__ u_next_all, int64_t u_stride) {
+  static_assert(KPP_ST / 64 >= PP_TMAX, "one wave per candidate");
   __shared__ double pots[PP_TMAX];
   __shared__ double wtot[KPP_ST / 64];
   __shared__ int s_sel;
   const int run_id = blockIdx.x;
   const double* bpart = bpart_all + (int64_t)run_id * T;                 // column base; rows are RT apart
   const int32_t* cand = cand_all + (int64_t)run_id * T;                  // this step's candidates (T per run)
-  int32_t* cand_next = cand_next_all + (int64_t)run_id * Tn;             // the next step's (Tn per run), in the other buffer: the runs' workgroups are concurrent
+  int32_t* cand_next = cand_next_all + (int64_t)run_id * Tn;             // the next step's (Tn per run)
   double* csum = csum_all + (int64_t)run_id * nblk;
   const float* nd_cur = nd_cur_all + (int64_t)run_id * T * N;
-  const double* u_next = u_next_all ? u_next_all + (int64_t)run_id * u_stride : nullptr;
   const int i = threadIdx.x, lane = i & 63, wave = i >> 6;
   if (wave < T) {
     double a = 0.0;
@@ -1802,11 +1636,12 @@ __global__ __launch_bounds__(KPP_ST) void kpp_select_batch(const double* __restr
   }
   __syncthreads();
   const int b = s_sel;
+  // inclusive scan of column b: thread i owns the run of `per` consecutive chunks [i * per, ...)
   const int64_t per = (nblk + KPP_ST - 1) / KPP_ST;
   const int64_t c0 = (int64_t)i * per, c1 = c0 + per < nblk ? c0 + per : nblk;
   double run = 0.0;
   for (int64_t c = c0; c < c1; ++c) run += bpart[c * RT + b];
-  double inc = run;
+  double inc = run;                                                     // inclusive scan of the run totals inside the wave
   for (int d = 1; d < 64; d <<= 1) {
     const double u = __shfl_up(inc, d);
     if (lane >= d) inc += u;
@@ -1814,34 +1649,15 @@ __global__ __launch_bounds__(KPP_ST) void kpp_select_batch(const double* __restr
   if (lane == 63) wtot[wave] = inc;
   __syncthreads();
   double woff = 0.0;
-  for (int w = 0; w < wave; ++w) woff += wtot[w];
-  double a = woff + inc - run;
+  for (int w = 0; w < wave; ++w) woff += wtot[w];                       // <= 15 adds, same order in every thread of the wave
+  double a = woff + inc - run;                                          // exclusive offset of this thread's run
   for (int64_t c = c0; c < c1; ++c) { a += bpart[c * RT + b]; csum[c] = a; }
-  if (!u_next) return;
-  __syncthreads();
+  if (!u_next_all) return;
+  __syncthreads();                                                       // csum is complete (and visible: one workgroup per run)
   if (wave >= Tn) return;
-  const float* v = nd_cur + (int64_t)b * N;
-  const double x = u_next[wave] * pots[b];
-  int64_t lo = 0, hi = nblk;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (csum[mid] < x) lo = mid + 1; else hi = mid;
-  }
-  int64_t res = N;
-  if (lo < nblk) {
-    const double base = lo ? csum[lo - 1] : 0.0;
-    const int64_t e = lo * KPP_CH + lane;
-    const double part = e < N ? (double)v[e] : 0.0;
-    double runs = base, incl = 0.0;
-    for (int l = 0; l < 64; ++l) {
-      runs += __shfl(part, l);
-      if (l == lane) incl = runs;
-    }
-    const unsigned long long m = __ballot(incl >= x && e < N);
-    res = m ? lo * KPP_CH + (__ffsll((long long)m) - 1) : ((lo + 1) * KPP_CH < N ? (lo + 1) * KPP_CH : N);
-  }
-  if (res > N - 1) res = N - 1;
-  if (lane == 0) cand_next[wave] = (int32_t)res;
+  // the run's uniforms are addressed here: a conditional pointer formed at the top serialises the kernel-argument loads (0.2 us per launch)
+  const int32_t next = kpp_search(nd_cur + (int64_t)b * N, N, csum, nblk, u_next_all[(int64_t)run_id * u_stride + wave] * pots[b], lane);
+  if (lane == 0) cand_next[wave] = next;
 }
 
 // ------------------------------------ C ABI ------------------------------------------------
@@ -2281,65 +2097,55 @@ extern "C" int slic_kmeanspp_step(const float* X, int64_t N, int D, int ldx, con
   return SLIC_OK;
 }
 
-// workspace: newdist [2][T][N] f32 | bpart [nblk][T] f64 | csum [nblk] f64 | cur_pot f64 | cand [T] i32 | sel i32
-extern "C" size_t slic_kmeanspp_run_workspace_bytes(int64_t N, int T) {
-  const int64_t nblk = slic_cdiv(N, KPP_CH);
-  return slic_align_up((size_t)2 * T * N * 4, 256) + slic_align_up((size_t)nblk * T * 8, 256) +
-         slic_align_up((size_t)nblk * 8, 256) + 256 + slic_align_up((size_t)T * 4, 256) + 256;
-}
-
-extern "C" int slic_kmeanspp_run(const float* X, int64_t N, int D, int ldx, int first, int K, int T,
-                                 const double* uniforms, int32_t* idx_out, const float* Xp, const float* xnorm,
-                                 void* workspace, void* stream) {
-  SLIC_REQUIRE(X && uniforms && idx_out && workspace, "slic_kmeanspp_run: null pointer");
-  SLIC_REQUIRE(N > 0 && K > 0 && K <= N && first >= 0 && first < N && T >= 1 && T <= PP_TMAX && D % 4 == 0 && ldx % 4 == 0 &&
-               (size_t)T * D * 4 <= 48 * 1024, "slic_kmeanspp_run: need 1 <= T <= %d, D %% 4 == 0, T*D*4 <= 48 KiB", PP_TMAX);
-  hipStream_t st = S_(stream);
-  const int64_t nblk = slic_cdiv(N, KPP_CH);
-  SlicCarver w(workspace);
-  float* nd = w.take<float>((size_t)2 * T * N);
-  double* bpart = w.take<double>((size_t)nblk * T);
-  double* csum = w.take<double>((size_t)nblk);
-  double* cur_pot = w.take<double>(1);
-  int32_t* cand = w.take<int32_t>(T);
-  int32_t* sel = w.take<int32_t>(1);
-  // matrix-pipe distances when the caller has the k-permuted copy and the row norms (and 32-bit offsets reach every row)
-  const bool mfma = Xp && xnorm && D % 8 == 0 && (int64_t)N * ldx * 4 < (1ll << 31);
-  const size_t lds_m = (size_t)2 * (128 + 32) * SLIC_RT_BK * sizeof(float);
-  if (mfma) SLIC_LDS_LIMIT(kpp_dist_mfma, lds_m);
-  const unsigned nblk_m = (unsigned)slic_cdiv(N, 128);
-  // centre 0: one candidate (the uniformly drawn row), no closest yet
-  SLIC_HIP_CHECK(hipMemcpyAsync(cand, &first, sizeof(int32_t), hipMemcpyHostToDevice, st));
-  if (mfma) kpp_dist_mfma<<<dim3(nblk_m), dim3(256), lds_m, st>>>(Xp, xnorm, N, D, ldx, cand, 1, nullptr, nullptr, nd, bpart, nblk);
-  else kpp_dist_rows<8><<<dim3((unsigned)nblk), dim3(256), (size_t)D * 4, st>>>(X, N, D, ldx, cand, 1, nullptr, nullptr, nd, bpart);
-  SLIC_LAUNCH_CHECK();
-  // every select also draws the next step's T candidates (uniforms of step c at uniforms + (c - 1) T) from the distances it chose
-  kpp_select<<<dim3(1), dim3(KPP_ST), 0, st>>>(bpart, nblk, 1, cand, sel, cur_pot, csum, idx_out, nd, N, K > 1 ? uniforms : nullptr, T);
-  SLIC_LAUNCH_CHECK();
-  for (int c = 1; c < K; ++c) {
-    const float* prev = nd + (size_t)((c - 1) & 1) * T * N;
-    float* cur = nd + (size_t)(c & 1) * T * N;
-    if (mfma) kpp_dist_mfma<<<dim3(nblk_m), dim3(256), lds_m, st>>>(Xp, xnorm, N, D, ldx, cand, T, prev, sel, cur, bpart, nblk);
-    else if (T <= 8) kpp_dist_rows<8><<<dim3((unsigned)nblk), dim3(256), (size_t)T * D * 4, st>>>(X, N, D, ldx, cand, T, prev, sel, cur, bpart);
-    else kpp_dist_rows<16><<<dim3((unsigned)nblk), dim3(256), (size_t)T * D * 4, st>>>(X, N, D, ldx, cand, T, prev, sel, cur, bpart);
-    SLIC_LAUNCH_CHECK();
-    kpp_select<<<dim3(1), dim3(KPP_ST), 0, st>>>(bpart, nblk, T, cand, sel, cur_pot, csum, idx_out + c, cur, N,
-                                                 c + 1 < K ? uniforms + (size_t)c * T : nullptr, T);
-    SLIC_LAUNCH_CHECK();
-  }
-  return SLIC_OK;
-}
-
-// All R initialisations of KMeans(n_init = R) in lock-step (kpp_dist_mfma_batch / kpp_select_batch above): firsts[r] = run r's
-// uniformly drawn first row, uniforms [R][K - 1][T] (host-drawn in the sequential loop's order), idx_out [R][K].
-// Needs the k-permuted copy and the row norms (the matrix-pipe distance kernel); R * T <= 160.
+// workspace: newdist [2][R][T][N] f32 | bpart [nblk][R * T] f64 | csum [R][nblk] f64 | pot [R] f64 | cand [2][R * T] i32 | sel [R] i32
 extern "C" size_t slic_kmeanspp_run_batch_workspace_bytes(int64_t N, int T, int R) {
   const int64_t nblk = slic_cdiv(N, KPP_CH);
   return slic_align_up((size_t)2 * R * T * N * 4, 256) + slic_align_up((size_t)nblk * R * T * 8, 256) +
          slic_align_up((size_t)R * nblk * 8, 256) + slic_align_up((size_t)R * 8, 256) + 2 * slic_align_up((size_t)R * T * 4, 256) +
          slic_align_up((size_t)R * 4, 256);
 }
+extern "C" size_t slic_kmeanspp_run_workspace_bytes(int64_t N, int T) { return slic_kmeanspp_run_batch_workspace_bytes(N, T, 1); }
 
+// The k-means++ sequence of R runs in lock-step (R = 1: one run): firsts[r] = run r's first row (host memory), uniforms [R][K - 1][T],
+// idx_out [R][K].  dist(RT, T, Tprev, cand, prev, sel, cur, bpart) launches the distance kernel for RT = R * T candidate rows, T per run,
+// against the previous step's distances prev ([R][Tprev][N], run r's closest = its row sel[r]; nullptr at centre 0).
+template <class Dist>
+static int kpp_run_all(int64_t N, int R, const int32_t* firsts, int K, int T, const double* uniforms, int32_t* idx_out, void* workspace,
+                       hipStream_t st, Dist dist) {
+  const int64_t nblk = slic_cdiv(N, KPP_CH);
+  SlicCarver w(workspace);
+  float* nd = w.take<float>((size_t)2 * R * T * N);
+  double* bpart = w.take<double>((size_t)nblk * R * T);
+  double* csum = w.take<double>((size_t)R * nblk);
+  double* pot = w.take<double>(R);
+  int32_t* cand = w.take<int32_t>((size_t)R * T);
+  int32_t* cand_next = w.take<int32_t>((size_t)R * T);
+  int32_t* sel = w.take<int32_t>(R);
+  // centre 0 of every run: one candidate each (the uniformly drawn row), no closest yet
+  SLIC_HIP_CHECK(hipMemcpyAsync(cand, firsts, (size_t)R * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  int rc = dist(R, 1, 1, cand, nullptr, sel, nd, bpart);
+  if (rc) return rc;
+  // every select also draws the next step's T candidates (uniforms of step c at uniforms + (c - 1) T) from the distances it chose
+  const int64_t ustride = (int64_t)(K - 1) * T;
+  kpp_select<<<dim3(R), dim3(KPP_ST), 0, st>>>(bpart, nblk, 1, R, T, cand, cand_next, sel, pot, csum, idx_out, K, nd, N,
+                                               K > 1 ? uniforms : nullptr, ustride);
+  SLIC_LAUNCH_CHECK();
+  for (int c = 1; c < K; ++c) {
+    std::swap(cand, cand_next);
+    const float* prev = nd + (size_t)((c - 1) & 1) * R * T * N;
+    float* cur = nd + (size_t)(c & 1) * R * T * N;
+    rc = dist(R * T, T, c == 1 ? 1 : T, cand, prev, sel, cur, bpart);
+    if (rc) return rc;
+    kpp_select<<<dim3(R), dim3(KPP_ST), 0, st>>>(bpart, nblk, T, R * T, T, cand, cand_next, sel, pot, csum, idx_out + c, K, cur, N,
+                                                 c + 1 < K ? uniforms + (size_t)c * T : nullptr, ustride);
+    SLIC_LAUNCH_CHECK();
+  }
+  return SLIC_OK;
+}
+
+// All R initialisations of KMeans(n_init = R) in lock-step: firsts[r] = run r's uniformly drawn first row, uniforms [R][K - 1][T]
+// (host-drawn in the sequential loop's order), idx_out [R][K].  Needs the k-permuted copy and the row norms (the matrix-pipe distance
+// kernel); R * T <= 160.
 extern "C" int slic_kmeanspp_run_batch(const float* Xp, const float* xnorm, int64_t N, int D, int ldx, int R, const int32_t* firsts,
                                        int K, int T, const double* uniforms, int32_t* idx_out, void* workspace, void* stream) {
   SLIC_REQUIRE(Xp && xnorm && firsts && uniforms && idx_out && workspace, "slic_kmeanspp_run_batch: null pointer");
@@ -2347,24 +2153,17 @@ extern "C" int slic_kmeanspp_run_batch(const float* Xp, const float* xnorm, int6
                (int64_t)N * ldx * 4 < (1ll << 31), "slic_kmeanspp_run_batch: need 1 <= T <= %d, R * T <= 160, D %% 8 == 0, N * ldx * 4 < 2 GiB", PP_TMAX);
   for (int r = 0; r < R; ++r) SLIC_REQUIRE(firsts[r] >= 0 && firsts[r] < N, "slic_kmeanspp_run_batch: firsts[%d] out of range", r);
   hipStream_t st = S_(stream);
-  const int64_t nblk = slic_cdiv(N, KPP_CH);
-  SlicCarver w(workspace);
-  float* nd = w.take<float>((size_t)2 * R * T * N);
-  double* bpart = w.take<double>((size_t)nblk * R * T);
-  double* csum = w.take<double>((size_t)R * nblk);
-  double* pot = w.take<double>(R);
-  int32_t* candA = w.take<int32_t>((size_t)R * T);
-  int32_t* candB = w.take<int32_t>((size_t)R * T);
-  int32_t* sel = w.take<int32_t>(R);
   const unsigned nblk_m = (unsigned)slic_cdiv(N, 128);
-  auto dist = [&](int RT, int Tc, int Tprev, const int32_t* cand, const float* prev, float* cur) -> int {
+  const int64_t nblk = slic_cdiv(N, KPP_CH);
+  return kpp_run_all(N, R, firsts, K, T, uniforms, idx_out, workspace, st,
+                     [&](int RT, int Tc, int Tprev, const int32_t* cand, const float* prev, const int32_t* sel, float* cur, double* bpart) -> int {
     const int ng = (RT + 31) / 32;
     const size_t lds = (size_t)2 * (128 + 32 * ng) * SLIC_RT_BK * sizeof(float);
 #define KPP_BATCH(NG)                                                                                                              \
     {                                                                                                                              \
-      SLIC_LDS_LIMIT(kpp_dist_mfma_batch<NG>, lds);                                                                                \
-      kpp_dist_mfma_batch<NG><<<dim3(nblk_m), dim3(256), lds, st>>>(Xp, xnorm, N, D, ldx, cand, RT, Tc, Tprev, prev, sel, cur,     \
-                                                                   bpart, nblk);                                                   \
+      SLIC_LDS_LIMIT(kpp_dist_mfma<NG>, lds);                                                                                      \
+      kpp_dist_mfma<NG><<<dim3(nblk_m), dim3(256), lds, st>>>(Xp, xnorm, N, D, ldx, cand, RT, Tc, Tprev, prev, sel, cur, bpart,    \
+                                                             nblk);                                                                \
     }
     switch (ng) {
       case 1: KPP_BATCH(1) break;
@@ -2376,27 +2175,28 @@ extern "C" int slic_kmeanspp_run_batch(const float* Xp, const float* xnorm, int6
 #undef KPP_BATCH
     SLIC_LAUNCH_CHECK();
     return SLIC_OK;
-  };
-  // centre 0 of every run: one candidate each (the uniformly drawn row), no closest yet
-  SLIC_HIP_CHECK(hipMemcpyAsync(candA, firsts, (size_t)R * sizeof(int32_t), hipMemcpyHostToDevice, st));
-  int rc = dist(R, 1, 1, candA, nullptr, nd);
-  if (rc) return rc;
-  const int64_t ustride = (int64_t)(K - 1) * T;
-  kpp_select_batch<<<dim3(R), dim3(KPP_ST), 0, st>>>(bpart, nblk, 1, R, T, candA, candB, sel, pot, csum, idx_out, K, nd, N,
-                                                     K > 1 ? uniforms : nullptr, ustride);
-  SLIC_LAUNCH_CHECK();
-  int32_t *cc = candB, *cn2 = candA;
-  for (int c = 1; c < K; ++c) {
-    const float* prev = nd + (size_t)((c - 1) & 1) * R * T * N;
-    float* cur = nd + (size_t)(c & 1) * R * T * N;
-    rc = dist(R * T, T, c == 1 ? 1 : T, cc, prev, cur);
-    if (rc) return rc;
-    kpp_select_batch<<<dim3(R), dim3(KPP_ST), 0, st>>>(bpart, nblk, T, R * T, T, cc, cn2, sel, pot, csum, idx_out + c, K, cur, N,
-                                                       c + 1 < K ? uniforms + (size_t)c * T : nullptr, ustride);
+  });
+}
+
+// One run.  With the k-permuted copy and the row norms (and 32-bit offsets reaching every row) it is the lock-step sequence at R = 1 on the
+// matrix pipe; without them the same sequence with kpp_dist_rows: at R = 1 its `prev + (*sel) * N` is the row the run-indexed layout means.
+extern "C" int slic_kmeanspp_run(const float* X, int64_t N, int D, int ldx, int first, int K, int T,
+                                 const double* uniforms, int32_t* idx_out, const float* Xp, const float* xnorm,
+                                 void* workspace, void* stream) {
+  SLIC_REQUIRE(X && uniforms && idx_out && workspace, "slic_kmeanspp_run: null pointer");
+  SLIC_REQUIRE(N > 0 && K > 0 && K <= N && first >= 0 && first < N && T >= 1 && T <= PP_TMAX && D % 4 == 0 && ldx % 4 == 0 &&
+               (size_t)T * D * 4 <= 48 * 1024, "slic_kmeanspp_run: need 1 <= T <= %d, D %% 4 == 0, T*D*4 <= 48 KiB", PP_TMAX);
+  if (Xp && xnorm && D % 8 == 0 && (int64_t)N * ldx * 4 < (1ll << 31))
+    return slic_kmeanspp_run_batch(Xp, xnorm, N, D, ldx, 1, &first, K, T, uniforms, idx_out, workspace, stream);
+  hipStream_t st = S_(stream);
+  const unsigned nblk = (unsigned)slic_cdiv(N, KPP_CH);
+  return kpp_run_all(N, 1, &first, K, T, uniforms, idx_out, workspace, st,
+                     [&](int, int Tc, int, const int32_t* cand, const float* prev, const int32_t* sel, float* cur, double* bpart) -> int {
+    if (Tc <= 8) kpp_dist_rows<8><<<dim3(nblk), dim3(256), (size_t)Tc * D * 4, st>>>(X, N, D, ldx, cand, Tc, prev, sel, cur, bpart);
+    else kpp_dist_rows<16><<<dim3(nblk), dim3(256), (size_t)Tc * D * 4, st>>>(X, N, D, ldx, cand, Tc, prev, sel, cur, bpart);
     SLIC_LAUNCH_CHECK();
-    int32_t* t = cc; cc = cn2; cn2 = t;
-  }
-  return SLIC_OK;
+    return SLIC_OK;
+  });
 }
 
 extern "C" size_t slic_cumsum_search_workspace_bytes(int64_t N) {
