@@ -389,6 +389,17 @@ int slic_ncdhw_to_ndhwc(const float* x, int B, int C, int64_t S, int Cp, float* 
  * the W-run stem operand */
 int slic_ncdhw_to_ndhwc_wpad(const float* x, int B, int C, int64_t R, int W, int pad_left, int Wp, float* y, void* stream);
 
+/* Data gradient of the stem convolution with respect to the clip (csrc/stem_dgrad.hip): kernel kt x 7 x 7, stride (st, 2, 2),
+ * pad (kt / 2, 3, 3), 1 <= C <= 4 input channels, N % 8 == 0 output channels, kt odd <= 7, st 1 or 2, any T, H, W.
+ * dz [B, To, Ho, Wo, N] (NDHWC, To = (T - 1) / st + 1, Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1, 16-byte aligned) ->
+ * dx [B, C, T, H, W] (NCDHW, the clip's own layout; every element is written).  Exact fp32, fixed summation order, no atomics.
+ * Wp: kt * 16 * N * 16 floats from slic_pack_weight_stem_dgrad — W in the reference layout [N, C, kt, 7, 7] spread over the 4 x 4
+ * (h, w) offsets into dz and the C x 2 x 2 (channel, h parity, w parity) columns, zero where a parity class has no tap.
+ * Any other shape: non-zero return with slic_last_error set. */
+int slic_pack_weight_stem_dgrad(const float* W, int N, int C, int kt, float* Wp, void* stream);
+int slic_conv_stem_dgrad(const float* dz, const float* Wp, int B, int C, int T, int H, int W, int N, int kt, int st, float* dx,
+                         void* stream);
+
 /* SyncBatchNorm (online_train.py:466-468 -> torch.nn.SyncBatchNorm.convert_sync_batchnorm): the rank-local halves of
  * slic_bn_finalize / slic_bn_bwd*, with the collective left to the caller (torch.distributed over RCCL).
  *   forward : slic_bn_merge_stats -> stats[0..C) = sum, stats[C..2C) = M2 (doubles); the caller writes its sample count to

@@ -86,6 +86,8 @@ SIGNATURES = {
     "slic_conv_wgrad_wino": (I, [P, P, I, P, P, P, P]),
     "slic_ncdhw_to_ndhwc": (I, [P, I, I, L, I, P, P]),
     "slic_ncdhw_to_ndhwc_wpad": (I, [P, I, I, L, I, I, I, P, P]),
+    "slic_pack_weight_stem_dgrad": (I, [P, I, I, I, P, P]),
+    "slic_conv_stem_dgrad": (I, [P, P, I, I, I, I, I, I, I, I, P, P]),
     # batch norm / pool
     "slic_bn_finalize_workspace_bytes": (c_size_t, [I, I]),
     "slic_bn_finalize": (I, [P, I, I, I, L, F, F, P, P, P, P, P, P, P, P, P, P]),

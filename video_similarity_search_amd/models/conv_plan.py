@@ -66,6 +66,10 @@ def _env(name, default=None):
     return default if v is None else os.environ.decodevalue(v)
 
 
+# launches by flavour (diagnostics / tests); models/resnet.py adds its own keys to the same dictionary
+COUNTS = {"stem_dgrad": 0, "wgrad": 0}
+
+
 def _tap_mask(oa, ob, oc):
     """bit (7*dim + o + 3): the row's precomputed in-bounds mask must contain all three"""
     assert max(abs(oa), abs(ob), abs(oc)) <= 3, "tap offsets beyond +-3 are not supported by the row mask"
@@ -157,6 +161,8 @@ class ConvPlan:
         self.wino2_wgrad = bool(wino2_wgrad)
         assert not self.wino2_wgrad or base, "transposed 2-D Winograd weight gradient: a Winograd plan"
         self._wu = self._wud = None
+        self._wsd = self._wsd_key = None           # input_grad: the stem data-gradient operand and the weight it was packed from
+        self._dgrad_plan = None                    # input_grad's fallback: a sibling plan on the generic data-gradient kernels
         self._wino_tabs = {}
         self._wino2_tabs = {}
         if self.wrun:
@@ -260,7 +266,7 @@ class ConvPlan:
         self.tab_fwd = torch.from_numpy(tab).to(self.device)
         self.tap_fwd = None
         self.Kp = self.nchunks_fwd * 4
-        self.dgrad_classes = []                              # the clip needs no gradient
+        self.dgrad_classes = []                              # the W-run operand has no transposed form: the clip's gradient is input_grad()
         self._wp = self._wd = None
         self._wp_key = self._wd_key = None
         self._row_tabs = {}
@@ -291,7 +297,9 @@ class ConvPlan:
         return (weight.data_ptr(), weight._version)
 
     def drop_packs(self):
-        self._wp_key = self._wd_key = None
+        self._wp_key = self._wd_key = self._wsd_key = None
+        if self._dgrad_plan is not None and self._dgrad_plan is not self:
+            self._dgrad_plan.drop_packs()
 
     def pack_fwd(self, weight, fresh=False):
         if self.wino:
@@ -316,7 +324,7 @@ class ConvPlan:
 
     def pack_dgrad(self, weight, fresh=False):
         if self.wrun:
-            raise _lib.SlicError("the W-run operand serves forward and weight gradient only (the clip needs no gradient)")
+            raise _lib.SlicError("the W-run operand serves forward and weight gradient only (the clip's gradient is input_grad())")
         if self.wino:
             if not fresh and self._wd_key is not None and self._wd_key == self._wkey(weight):
                 return self._wud
@@ -643,6 +651,49 @@ class ConvPlan:
                 self._launch(a, variant)
         return dx if bwd is None else (dx, part)
 
+    # ------------------------------------------------------------------ gradient with respect to an NCDHW input (the clip)
+    def stem_dgrad_ok(self):
+        """the shapes slic_conv_stem_dgrad takes: kt x 7 x 7 / (st, 2, 2) / pad (kt // 2, 3, 3), C <= 4, N % 8 == 0, kt odd <= 7, st 1 or 2"""
+        kt = self.kernel[0]
+        return (self.C <= 4 and self.N % 8 == 0 and self.kernel[1:] == (7, 7) and kt % 2 == 1 and kt <= 7 and
+                self.stride[0] in (1, 2) and self.stride[1:] == (2, 2) and self.pad == (kt // 2, 3, 3))
+
+    def input_grad(self, dz, weight, B, out=None):
+        """dz: [B, To, Ho, Wo, N] -> the gradient with respect to the plan's NCDHW input, [B, C, T, H, W] (written into `out` when given).
+        The stem shapes run slic_conv_stem_dgrad, which writes the clip's layout directly (SLIC_STEM_DGRAD=0: off); any other shape —
+        and a W-run plan has no transposed operand of its own — goes through a sibling plan on the generic data-gradient kernels,
+        whose [B, T, H, W, Cs] result is then copied to NCDHW without its pad channels."""
+        T, H, W = self.in_dims
+        assert tuple(dz.shape) == (B,) + self.out_dims + (self.N,), (tuple(dz.shape), (B,) + self.out_dims + (self.N,))
+        dx = out if out is not None else torch.empty((B, self.C, T, H, W), dtype=torch.float32, device=dz.device)
+        assert tuple(dx.shape) == (B, self.C, T, H, W) and dx.is_contiguous() and dx.dtype == torch.float32
+        chunks = self._chunks(B)
+        if chunks is not None:
+            for b0, b1 in chunks:
+                self.input_grad(dz[b0:b1], weight, b1 - b0, dx[b0:b1])
+            return dx
+        dz = dz.contiguous()
+        if self.stem_dgrad_ok() and _env("SLIC_STEM_DGRAD", "1") != "0":
+            if dz.data_ptr() % 16:
+                dz = dz.clone()
+            if self._wsd_key is None or self._wsd_key != self._wkey(weight):
+                if self._wsd is None:
+                    self._wsd = torch.empty(self.kernel[0] * 16 * self.N * 16, dtype=torch.float32, device=self.device)
+                call("slic_pack_weight_stem_dgrad", ptr(weight), self.N, self.C, self.kernel[0], ptr(self._wsd), stream())
+                self._wsd_key = self._wkey(weight)
+            COUNTS["stem_dgrad"] += 1
+            call("slic_conv_stem_dgrad", ptr(dz), ptr(self._wsd), B, self.C, T, H, W, self.N, self.kernel[0], self.stride[0],
+                 ptr(dx), stream())
+            return dx
+        sib = self._dgrad_plan
+        if sib is None:
+            sib = self if not (self.wrun or self.wino) else ConvPlan(self.C, self.N, self.kernel, self.stride, self.pad, self.in_dims,
+                                                                     self.device, wrun=False, wino=False)
+            self._dgrad_plan = sib
+        d5 = sib.dgrad(dz, sib.pack_dgrad(weight), B)
+        dx.copy_(d5[..., :self.C].permute(0, 4, 1, 2, 3))
+        return dx
+
     def tap_classes(self):
         """the parity classes of the data gradient that have at least one tap (the positions dgrad(skip_empty=True) writes)"""
         return {dc["cls"] for dc in self.dgrad_classes if dc["nchunks"] > 0}
@@ -694,6 +745,7 @@ class ConvPlan:
                 if i:
                     dW.add_(tmp)
             return dW
+        COUNTS["wgrad"] += 1
         a = self._fwd_args(x, B)
         if self.wino2_wgrad:
             # transposed F(4, 3) x F(2, 3): one workgroup of 512 threads per kt, 64 x 64 block and slice of the 2 x 4

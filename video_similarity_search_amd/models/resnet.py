@@ -24,7 +24,7 @@ from functools import partial
 
 from .. import _lib
 from .._lib import call, ptr, stream
-from .conv_plan import ConvPlan
+from .conv_plan import COUNTS, ConvPlan
 from .dropout import apply_mask, next_seed_offset
 
 BN_EPS = 1e-5
@@ -102,7 +102,8 @@ class _Bn:
         self.frozen = False
 
 
-COUNTS = {"bn_bwd": 0, "bn_bwd_fused": 0, "probe_pass": 0, "segments_saved": 0}     # launches / passes by flavour (diagnostics / tests)
+# launches / passes by flavour (diagnostics / tests); conv_plan's dictionary, which counts "stem_dgrad" and "wgrad" per launch
+COUNTS.update({"bn_bwd": 0, "bn_bwd_fused": 0, "probe_pass": 0, "segments_saved": 0})
 
 
 _GRAD_VIEWS = [None]       # the pass's {parameter: DistributedDataParallel bucket view} (misc.distributed_helper.data_parallel), or None
@@ -248,18 +249,25 @@ class _Engine:
             dpad[:, :self.n_cls].copy_(dy)
             dy = dpad
         d5 = dy.view(B, 1, 1, 1, self.n_pad)
-        gw, gb = new_like(lin.weight), new_like(lin.bias)
-        if self.n_pad == self.n_cls:
-            self.lin.wgrad(ctx["xin"].view(B, 1, 1, 1, self.feat), d5, B, gw)
-            call("slic_colsum", ptr(dy), B, self.n_pad, ptr(gb), stream())
-        else:
-            gwp = torch.empty(self.n_pad, lin.in_features, dtype=torch.float32, device=dy.device)
-            gbp = torch.empty(self.n_pad, dtype=torch.float32, device=dy.device)
-            self.lin.wgrad(ctx["xin"].view(B, 1, 1, 1, self.feat), d5, B, gwp)
-            call("slic_colsum", ptr(dy), B, self.n_pad, ptr(gbp), stream())
-            gw.copy_(gwp[:self.n_cls])
-            gb.copy_(gbp[:self.n_cls])
-        grads = {lin.weight: gw, lin.bias: gb}
+        grads = {}
+        if lin.weight.requires_grad:               # a frozen weight launches no weight gradient
+            gw = new_like(lin.weight)
+            if self.n_pad == self.n_cls:
+                self.lin.wgrad(ctx["xin"].view(B, 1, 1, 1, self.feat), d5, B, gw)
+            else:
+                gwp = torch.empty(self.n_pad, lin.in_features, dtype=torch.float32, device=dy.device)
+                self.lin.wgrad(ctx["xin"].view(B, 1, 1, 1, self.feat), d5, B, gwp)
+                gw.copy_(gwp[:self.n_cls])
+            grads[lin.weight] = gw
+        if lin.bias.requires_grad:
+            gb = new_like(lin.bias)
+            if self.n_pad == self.n_cls:
+                call("slic_colsum", ptr(dy), B, self.n_pad, ptr(gb), stream())
+            else:
+                gbp = torch.empty(self.n_pad, dtype=torch.float32, device=dy.device)
+                call("slic_colsum", ptr(dy), B, self.n_pad, ptr(gbp), stream())
+                gb.copy_(gbp[:self.n_cls])
+            grads[lin.bias] = gb
         if not need_dx:
             return None, grads
         dpool = self.lin.dgrad(d5, self.lin.pack_dgrad(ctx["lin_w"]), B).view(B, self.feat)
@@ -567,8 +575,10 @@ class _Engine:
         holder = ref() if ref is not None else None
         return holder.d if holder is not None else None
 
-    def seg_backward(self, si, ctx, dout, pid=None):
-        """returns (gradient wrt the segment input or None, {parameter: gradient}); pid = forward pass the context is from"""
+    def seg_backward(self, si, ctx, dout, pid=None, need_dinp=False):
+        """returns (gradient wrt the segment input or None, {parameter: gradient}); pid = forward pass the context is from.
+        need_dinp (segment 0): the clip requires a gradient — the NCDHW gradient is computed and returned.  A weight with
+        requires_grad == False launches no weight gradient (a saliency pass on a frozen encoder pays for data gradients only)."""
         net = self.net
         grads = {}
         B = dout.shape[0]
@@ -595,6 +605,8 @@ class _Engine:
         main = torch.cuda.current_stream()
 
         def wgrad_async(plan, x, dz, weight):
+            if not weight.requires_grad:
+                return None
             dW = new_like(weight)                       # allocated on the main stream: it outlives the side stream's use
             if side is None:
                 return plan.wgrad(x, dz, B, dW)
@@ -623,13 +635,17 @@ class _Engine:
             elif net.projection_head:
                 ah, h1, bnp, pooled = ctx["ah"], ctx["h1"], ctx["bnp"], ctx["pooled"]
                 d5 = dy.view(B, 1, 1, 1, -1)
-                grads[net.fc2.weight] = self.fc2.wgrad(ah.view(B, 1, 1, 1, -1), d5, B, new_like(net.fc2.weight))
-                grads[net.fc2.bias] = bias_grad(dy, net.fc2.bias)
+                if net.fc2.weight.requires_grad:
+                    grads[net.fc2.weight] = self.fc2.wgrad(ah.view(B, 1, 1, 1, -1), d5, B, new_like(net.fc2.weight))
+                if net.fc2.bias.requires_grad:
+                    grads[net.fc2.bias] = bias_grad(dy, net.fc2.bias)
                 dah = self.fc2.dgrad(d5, self.fc2.pack_dgrad(net.fc2.weight), B)
                 dh1, _, dg, db = self._bn_bwd(dah.view(B, -1), ah.view(B, -1), h1.view(B, -1), bnp, False)
                 grads[net.bn_proj.weight], grads[net.bn_proj.bias] = dg, db
-                grads[net.fc1.weight] = self.fc1.wgrad(pooled.view(B, 1, 1, 1, -1), dh1.view(B, 1, 1, 1, -1), B, new_like(net.fc1.weight))
-                grads[net.fc1.bias] = bias_grad(dh1.view(B, -1), net.fc1.bias)
+                if net.fc1.weight.requires_grad:
+                    grads[net.fc1.weight] = self.fc1.wgrad(pooled.view(B, 1, 1, 1, -1), dh1.view(B, 1, 1, 1, -1), B, new_like(net.fc1.weight))
+                if net.fc1.bias.requires_grad:
+                    grads[net.fc1.bias] = bias_grad(dh1.view(B, -1), net.fc1.bias)
                 dpool = self.fc1.dgrad(dh1.view(B, 1, 1, 1, -1), self.fc1.pack_dgrad(net.fc1.weight), B).view(B, -1)
             else:
                 dpool = dy
@@ -733,7 +749,7 @@ class _Engine:
                     dout = res
             join()
             return dout, grads
-        # stem: a0 = relu(bn1(conv1(x4))) (-> max-pool); the clip needs no gradient
+        # stem: a0 = relu(bn1(conv1(x4))) (-> max-pool); the clip's gradient only when it was asked for (need_dinp)
         if self.pool_in is not None:
             T, H, W = self.pool_in
             da0 = torch.empty_like(ctx["a0"])
@@ -746,8 +762,10 @@ class _Engine:
             dz0, _, dg0, db0 = self._bn_bwd(dout, ctx["a0"], ctx["z0"], ctx["bn0"], False)
         grads[net.bn1.weight], grads[net.bn1.bias] = dg0, db0
         grads[net.conv1.weight] = wgrad_async(self.stem, ctx["x4"], dz0, net.conv1.weight)
+        # the transposed stem convolution, on the main stream beside conv1's weight gradient: NCDHW, the clip's own layout
+        dinp = self.stem.input_grad(dz0, net.conv1.weight, B) if need_dinp else None
         join()
-        return None, grads
+        return dinp, grads
 
     # ------------------------------------------------------------------ whole passes (inference, tests, diagnostics)
     def forward(self, x, training, save):
@@ -821,7 +839,7 @@ class _SegmentFn(torch.autograd.Function):
         if ctx.saved is None:
             raise RuntimeError("the encoder's saved activations are released by its first backward pass: a second backward "
                                "through the same forward (retain_graph=True) is not supported — run the forward again")
-        dinp, grads = ctx.engine.seg_backward(ctx.si, ctx.saved, dout, ctx.pid)
+        dinp, grads = ctx.engine.seg_backward(ctx.si, ctx.saved, dout, ctx.pid, need_dinp=bool(ctx.si == 0 and ctx.inp_grad))
         ctx.saved = None
         ctx.holder = None
         ctx.engine._live.pop((ctx.pid, ctx.si), None)
@@ -965,18 +983,15 @@ def run_engine(eng, module, x):
             for si in range(eng.N_SEG - 1):
                 a, _ = eng.seg_forward(si, a, False, False)
         return _SegmentFn.apply(a, eng, eng.N_SEG - 1, False, *eng.seg_params(eng.N_SEG - 1))
-    if torch.is_grad_enabled() and params:
+    if torch.is_grad_enabled() and (params or x.requires_grad):
+        # also a fully frozen encoder under an input that requires a gradient (a saliency map, an adversarial probe): the reference
+        # back-propagates to the clip (models/resnet.py:255-312 is an ordinary autograd graph), and so do the segments — in the
+        # module's mode, data gradients only
         a = x
         eng.prepack(with_dgrad=True)
         for si in range(eng.N_SEG):
             a = _SegmentFn.apply(a, eng, si, bool(module.training), *eng.seg_params(si))
         return a
-    if torch.is_grad_enabled() and x.requires_grad:
-        # a fully frozen encoder under an input that wants a gradient: the reference would back-propagate to the clip
-        # (models/resnet.py:255-312 is an ordinary autograd graph); the stem here has no data gradient — say so instead of
-        # handing back a graph-less tensor
-        raise _lib.SlicError("ResNet.forward: the input requires a gradient but no encoder parameter does; the stem has no data "
-                             "gradient on this path (detach the clip, or leave at least one parameter trainable)")
     with torch.no_grad():
         return eng.forward(x, training=module.training, save=False)[0]
 
