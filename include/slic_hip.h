@@ -780,6 +780,32 @@ int slic_moco_ce_bwd(const float* q, const float* k, const float* memory, int B,
 int slic_moco_enqueue(float* memory, int64_t* queue_label, const float* k, const int64_t* k_label, int B, int K, int D, int index,
                       void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Clip transforms (coclr_utils/transforms.py: crop, pad, flip, bilinear resize, brightness / contrast / saturation jitter, random
+ * gray, normalise) on a batch of B clips as one gather kernel: uint8 [N, H, W, 3] or fp32 [3, N, H, W] per clip in, fp32
+ * [B, 3, N, Ho, Wo] out.  `table` is the device copy and `table_host` the host copy of the per-clip records and factor arrays (layout:
+ * the header comment of csrc/cliptf.hip); both entry points check on the host copy that every index a record can produce stays inside
+ * its clip and the table.  Built without a*b+c contraction; no atomics; the same inputs give the same bits.
+ * ---------------------------------------------------------------------------------------- */
+#define SLIC_CLIPTF_REC_BYTES 144
+#define SLIC_CLIPTF_MAX_OPS 4
+#define SLIC_CLIPTF_BRIGHTNESS 0
+#define SLIC_CLIPTF_CONTRAST 1
+#define SLIC_CLIPTF_SATURATION 2
+#define SLIC_CLIPTF_GRAY 3
+#define SLIC_CLIPTF_SRC_U8 0       /* uint8 NHWC, values 0..255 */
+#define SLIC_CLIPTF_SRC_U8_255 1   /* uint8 NHWC, divided by 255 */
+#define SLIC_CLIPTF_SRC_F32 2      /* fp32 CNHW */
+/* bytes of the per-(clip, frame, row band) partial sums a group with a contrast op needs */
+size_t slic_clip_transform_workspace_bytes(int B, int N, int Ho, int Wo);
+/* workspace <- partial sums of the gray of every frame as it is before its clip's contrast op (clips without one: untouched) */
+int slic_clip_transform_stats(const void* table, const void* table_host, size_t table_bytes, int B, int N, int Ho, int Wo, int kind,
+                              void* workspace, void* stream);
+/* out [B, 3, N, Ho, Wo] (16-byte aligned); normalize: apply the table's mean / std; workspace: what slic_clip_transform_stats left
+ * (NULL when no clip has a contrast op) */
+int slic_clip_transform_apply(const void* table, const void* table_host, size_t table_bytes, int B, int N, int Ho, int Wo, int kind,
+                              int normalize, const void* workspace, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

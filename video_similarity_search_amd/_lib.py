@@ -173,6 +173,10 @@ SIGNATURES = {
     "slic_moco_ce_fwd": (I, [P, P, P, I, I, I, F, P, P, P, P, P, P]),
     "slic_moco_ce_bwd": (I, [P, P, P, I, I, I, F, P, P, P, P, P, P, P]),
     "slic_moco_enqueue": (I, [P, P, P, P, I, I, I, I, P]),
+    # clip transforms
+    "slic_clip_transform_workspace_bytes": (c_size_t, [I, I, I, I]),
+    "slic_clip_transform_stats": (I, [P, P, c_size_t, I, I, I, I, I, P, P]),
+    "slic_clip_transform_apply": (I, [P, P, c_size_t, I, I, I, I, I, I, P, P, P]),
 }
 
 
