@@ -806,6 +806,36 @@ int slic_clip_transform_stats(const void* table, const void* table_host, size_t 
 int slic_clip_transform_apply(const void* table, const void* table_host, size_t table_bytes, int B, int N, int Ho, int Wo, int kind,
                               int normalize, const void* workspace, float* out, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Multi-tensor parameter updates: torch.optim.SGD / torch.optim.Adam (online_train.py:540-543, coclr_classify.py:206-208) and the
+ * MoCo key-encoder momentum update (models/infoNCE.py:87-90), each as ONE launch over every tensor of every parameter group.
+ *   map        device, int32 [n_items][2]: (tensor, chunk); chunk c is elements [c * CHUNK, (c + 1) * CHUNK) of its tensor,
+ *              CHUNK = slic_multi_tensor_chunk().  An entry outside its tensor is skipped, never followed.
+ *   desc       device, n_tensors records of SLIC_MT_DESC_BYTES (16-byte aligned):
+ *                u64 p, g, s1, s2   parameter, gradient, state (SGD: momentum_buffer, -; Adam: exp_avg, exp_avg_sq; EMA: p = key,
+ *                                   g = query, no state); fp32, contiguous, 4-byte aligned
+ *                i64 n              elements; offsets are 64-bit throughout, so n > 2^31 does not wrap
+ *                i32 flags, pad     SLIC_MT_VEC: every pointer used is 16-byte aligned (float4 path; else element by element)
+ *                f64 h[10]          SGD : lr, momentum, 1 - dampening, weight_decay
+ *                                   Adam: lr / bc1, 1 - beta1, beta2, 1 - beta2, eps, weight_decay, sqrt(bc2), bc = 1 - beta^step
+ *                                   EMA : m, 1 - m
+ *                                   computed by the caller in double, rounded to fp32 once on the device
+ *   desc_host  the host copy of desc, validated before every launch (pointers, alignment against the flag, state present)
+ * Formulas and the rounding of the chains (explicit fmaf, no other contraction): header comment of csrc/optim.hip.
+ * Adam is torch's Adam with L2 weight decay (not AdamW, no amsgrad); maximize is not supported.
+ * ---------------------------------------------------------------------------------------- */
+#define SLIC_MT_DESC_BYTES 128
+#define SLIC_MT_HYPER 10
+#define SLIC_MT_VEC 1
+#define SLIC_MT_NESTEROV 2
+#define SLIC_MT_FIRST 4      /* SGD: this tensor's first step, buf = g' */
+/* chunk length in elements (a multiple of 4) */
+int slic_multi_tensor_chunk(void);
+/* all_first != 0: every tensor is on its first step (as if each carried SLIC_MT_FIRST), so the table of step 1 serves step 2 */
+int slic_multi_sgd(const void* map, int n_items, const void* desc, const void* desc_host, int n_tensors, int all_first, void* stream);
+int slic_multi_adam(const void* map, int n_items, const void* desc, const void* desc_host, int n_tensors, void* stream);
+int slic_multi_ema(const void* map, int n_items, const void* desc, const void* desc_host, int n_tensors, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -177,6 +177,11 @@ SIGNATURES = {
     "slic_clip_transform_workspace_bytes": (c_size_t, [I, I, I, I]),
     "slic_clip_transform_stats": (I, [P, P, c_size_t, I, I, I, I, I, P, P]),
     "slic_clip_transform_apply": (I, [P, P, c_size_t, I, I, I, I, I, I, P, P, P]),
+    # multi-tensor optimizer step / EMA
+    "slic_multi_tensor_chunk": (I, []),
+    "slic_multi_sgd": (I, [P, I, P, P, I, I, P]),
+    "slic_multi_adam": (I, [P, I, P, P, I, P]),
+    "slic_multi_ema": (I, [P, I, P, P, I, P]),
 }
 
 
