@@ -558,6 +558,24 @@ size_t slic_cosine_topk_workspace_bytes(int Nq, int Ng, int k);
 int slic_cosine_topk_plan(int Nq, int Ng, int D, int k, int* out /* [6] */);
 int slic_cosine_topk(const float* Qn, int Nq, const float* Gn, int Ng, int D, int k, int self_mask,
                      int32_t* out_idx, float* out_dist, void* workspace, void* stream);
+/* The same search with the similarity GEMM on the bf16 MFMA as a CANDIDATE pass; the result is exact.  Rows rounded to bf16 give a coarse
+ * score c with |c - s| <= slic_cosine_topk_bf16_eps() (0.008: proven for L2-normalised rows, D <= 512, fp32 accumulation — DESIGN.md) of
+ * the fp32 score s.  Every row with c >= tau_q - eps (tau_q: the collect path's fp32 sample threshold) is a candidate; with c_k the k-th
+ * best coarse score, a row of the true top-k has c >= c_k - 2 eps, so those candidates are rescored from the fp32 rows and the k best of
+ * them are the global top-k (distance ascending, ties -> lower index, distance = clip(1 - s, 0, 2)).  A query with fewer than k
+ * candidates, or more than its slots, is redone by the fp32 streaming kernels: the result is exact for any data.
+ * Limits as slic_cosine_topk.  The bf16 pass runs where slic_cosine_topk_bf16_plan says so: inside the collect path's domain (Ng >= 32768,
+ * D <= 512) and where it measured faster than the fp32 path (Nq * Ng >= 1e9, D >= 128, k <= 50: profiles/topk_bf16.txt) — SLIC_TOPK_BF16=1: anywhere in that domain, for any
+ * k; SLIC_TOPK_BF16=0: nowhere.  Elsewhere the call IS slic_cosine_topk (and the workspace size is that call's).
+ *   plan   out[0] = 1 bf16 pass / 0 fp32 search, out[1] = candidate slots per query, out[2] = columns of a bf16 row (D rounded up to 16),
+ *          out[3] = queries per workgroup, out[4] = sampled gallery rows, out[5] = M (tau_q is the M-th best of the sample).  No device work.
+ *   stats  NULL or a DEVICE array of 3: {queries redone by the fp32 kernels, queries whose candidates overflowed their slots, candidates
+ *          of all queries (an overflowed query counts its slots)}; all 0 when the call took the fp32 search. */
+size_t slic_cosine_topk_bf16_workspace_bytes(int Nq, int Ng, int D, int k);
+int slic_cosine_topk_bf16_plan(int Nq, int Ng, int D, int k, int* out /* [6] */);
+int slic_cosine_topk_bf16(const float* Qn, int Nq, const float* Gn, int Ng, int D, int k, int self_mask,
+                          int32_t* out_idx, float* out_dist, int32_t* stats, void* workspace, void* stream);
+float slic_cosine_topk_bf16_eps(void);
 /* merge W per-GPU result lists ([W, Nq, k] distances ascending + GLOBAL gallery indices, -1 = empty slot) into the
  * k nearest per query (distance ascending, ties -> lower index): the step after the all-gather when the gallery is
  * sharded by rows across GPUs */

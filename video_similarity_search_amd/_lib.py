@@ -133,6 +133,10 @@ SIGNATURES = {
     "slic_cosine_topk_workspace_bytes": (c_size_t, [I, I, I]),
     "slic_cosine_topk_plan": (I, [I, I, I, I, P]),
     "slic_cosine_topk": (I, [P, I, P, I, I, I, I, P, P, P, P]),
+    "slic_cosine_topk_bf16_workspace_bytes": (c_size_t, [I, I, I, I]),
+    "slic_cosine_topk_bf16_plan": (I, [I, I, I, I, P]),
+    "slic_cosine_topk_bf16": (I, [P, I, P, I, I, I, I, P, P, P, P, P]),
+    "slic_cosine_topk_bf16_eps": (F, []),
     "slic_topk_merge_lists": (I, [P, P, I, I, I, P, P, P]),
     "slic_pairwise_euclidean": (I, [P, I, P, I, I, P, P]),
     "slic_euclidean_topk_workspace_bytes": (c_size_t, [I, I, I, I]),

@@ -1115,14 +1115,20 @@ static int topk_slices(int Nq, int Ng, int k) {
 // to reach.  Aim: 6 k + 100 candidates per query from a sample of <= ~4 % of the gallery, M = 4 .. 16: both failure events (fewer than k
 // candidates, more than TKC_CAP) stay below 1e-6 per query for any continuous score distribution (scripts/r5/topk_threshold_sim.py).
 struct TopkCollectPlan { bool on; int S1, per1, m1, gstep, cap, ms; };
+static TopkCollectPlan topk_collect_shape(int Nq, int Ng, int k);
 static TopkCollectPlan topk_collect_plan(int Nq, int Ng, int k) {
-  TopkCollectPlan c = {false, 0, 0, 0, 1, TKC_CAP, 0};
   // SLIC_TOPK_COLLECT: 0 = never, 1 = wherever the shape allows, unset = where it is faster: k >= 16 (10k x 100k x 512 on one MI355X, ms,
   // collect / streaming: k = 1 8.4 / 8.0, k = 10 8.3 / 8.0, k = 50 8.6 / 9.1, k = 88 8.8 / 12.4 — a short list costs the streaming kernels
   // almost nothing, while the collect pass pays ~0.3 ms for its sample and tests ~0.4 % of the scores one by one whatever k is)
   const char* e = getenv("SLIC_TOPK_COLLECT");
   const bool force = e && e[0] == '1';
-  if ((e && e[0] == '0') || Ng < 32768 || k > TK_KMAX || (k < 16 && !force)) return c;
+  if ((e && e[0] == '0') || (k < 16 && !force)) return TopkCollectPlan{false, 0, 0, 0, 1, TKC_CAP, 0};
+  return topk_collect_shape(Nq, Ng, k);
+}
+// the sample and the candidate slots for a shape inside the collect path's domain (on = false outside it), whatever the switches say
+static TopkCollectPlan topk_collect_shape(int Nq, int Ng, int k) {
+  TopkCollectPlan c = {false, 0, 0, 0, 1, TKC_CAP, 0};
+  if (Ng < 32768 || k > TK_KMAX) return c;
   const int qb = (int)slic_cdiv(Nq, TK_BQ);
   const double target = 6.0 * k + 100.0;
   int M = (int)(target * 0.04 + 0.5);
@@ -1148,12 +1154,18 @@ static TopkCollectPlan topk_collect_plan(int Nq, int Ng, int k) {
   return c;
 }
 
-extern "C" size_t slic_cosine_topk_workspace_bytes(int Nq, int Ng, int k) {
-  size_t b = 2 * slic_align_up((size_t)topk_slices(Nq, Ng, k) * Nq * k * 4, 256) + slic_align_up((size_t)Nq * 4, 256);
-  const TopkCollectPlan c = topk_collect_plan(Nq, Ng, k);
-  if (c.on)
-    b += 2 * slic_align_up((size_t)c.S1 * Nq * c.ms * 4, 256) + 3 * slic_align_up((size_t)Nq * 4, 256) + 256 +
+// what topk_stream and (c.on) the sample, thresholds and candidate buffers of the collect paths carve out of the workspace
+static size_t topk_stream_bytes(int Nq, int Ng, int k) {
+  return 2 * slic_align_up((size_t)topk_slices(Nq, Ng, k) * Nq * k * 4, 256) + slic_align_up((size_t)Nq * 4, 256);
+}
+static size_t topk_collect_bytes(const TopkCollectPlan& c, int Nq) {
+  return 2 * slic_align_up((size_t)c.S1 * Nq * c.ms * 4, 256) + 3 * slic_align_up((size_t)Nq * 4, 256) + 256 +
          slic_align_up((size_t)Nq * c.cap * 8, 256);
+}
+extern "C" size_t slic_cosine_topk_workspace_bytes(int Nq, int Ng, int k) {
+  size_t b = topk_stream_bytes(Nq, Ng, k);
+  const TopkCollectPlan c = topk_collect_plan(Nq, Ng, k);
+  if (c.on) b += topk_collect_bytes(c, Nq);
   return b;
 }
 
@@ -1213,6 +1225,25 @@ static int topk_stream(const float* Qn, int Nq, const float* Gn, int Ng, int D, 
   return SLIC_OK;
 }
 
+// the sample: S1 slices of per1 rows, every gstep-th row of the gallery, the m1 best of each (tiny heaps: LDS is no constraint), then
+// tau[q] = the m1-th best of the pooled sample, cnt[q] = 0, *nfail = 0
+template <bool EU>
+static int topk_sample_thresholds(const TopkCollectPlan& c, const float* Qn, int Nq, const float* Gn, int D, const float* ghn, float* pval1,
+                                  int32_t* pidx1, float* tau, int* cnt, int* nfail, hipStream_t st) {
+  const int kh = 1 + ((c.ms + 2) / 4) * 4;
+  const int pcap = TK_PC_MAX;
+  const size_t lds = (size_t)2 * 2 * TK_BQ * SLIC_RT_BK * sizeof(float) + (size_t)4 * kh * 32 * 8 + (size_t)4 * pcap * 64 * 8 + 16 + TK_EU_LDS(EU);
+  dim3 grid((unsigned)slic_cdiv(Nq, TK_BQ), (unsigned)c.S1);
+  const int ns = c.S1 * c.per1;
+  const auto kern = D > 256 ? topk_partial_qreg<16, 4, EU> : D > 128 ? topk_partial_qreg<8, 4, EU> : topk_partial_qreg<4, 4, EU>;
+  SLIC_LDS_LIMIT(kern, lds);
+  kern<<<grid, dim3(256), lds, st>>>(Qn, Nq, Gn, ns, D, c.ms, 0, c.per1, pcap, pval1, pidx1, nullptr, c.gstep, nullptr, nullptr, ghn);
+  SLIC_LAUNCH_CHECK();
+  topk_thresholds<<<dim3((unsigned)slic_cdiv(Nq, 4)), dim3(256), 0, st>>>(pval1, c.S1, Nq, c.ms, c.m1, tau, cnt, nfail);
+  SLIC_LAUNCH_CHECK();
+  return SLIC_OK;
+}
+
 // threshold -> collect -> select -> exact fallback for the queries whose candidate count fell outside [k, cap]
 template <bool EU>
 static int topk_collect(const TopkCollectPlan& c, const float* Qn, int Nq, const float* Gn, int Ng, int D, int k, int self_mask,
@@ -1224,19 +1255,10 @@ static int topk_collect(const TopkCollectPlan& c, const float* Qn, int Nq, const
   int* failq = w.take<int>((size_t)Nq);
   int* nfail = w.take<int>(64);
   unsigned long long* cand = w.take<unsigned long long>((size_t)Nq * c.cap);
-  // ---- 1. the sample: S1 slices of per1 rows, every gstep-th row of the gallery, the m1 best of each (tiny heaps: LDS is no constraint)
+  // ---- 1. the sample and the thresholds
   {
-    const int kh = 1 + ((c.ms + 2) / 4) * 4;
-    const int pcap = TK_PC_MAX;
-    const size_t lds = (size_t)2 * 2 * TK_BQ * SLIC_RT_BK * sizeof(float) + (size_t)4 * kh * 32 * 8 + (size_t)4 * pcap * 64 * 8 + 16 + TK_EU_LDS(EU);
-    dim3 grid((unsigned)slic_cdiv(Nq, TK_BQ), (unsigned)c.S1);
-    const int ns = c.S1 * c.per1;
-    const auto kern = D > 256 ? topk_partial_qreg<16, 4, EU> : D > 128 ? topk_partial_qreg<8, 4, EU> : topk_partial_qreg<4, 4, EU>;
-    SLIC_LDS_LIMIT(kern, lds);
-    kern<<<grid, dim3(256), lds, st>>>(Qn, Nq, Gn, ns, D, c.ms, 0, c.per1, pcap, pval1, pidx1, nullptr, c.gstep, nullptr, nullptr, ghn);
-    SLIC_LAUNCH_CHECK();
-    topk_thresholds<<<dim3((unsigned)slic_cdiv(Nq, 4)), dim3(256), 0, st>>>(pval1, c.S1, Nq, c.ms, c.m1, tau, cnt, nfail);
-    SLIC_LAUNCH_CHECK();
+    const int rc = topk_sample_thresholds<EU>(c, Qn, Nq, Gn, D, ghn, pval1, pidx1, tau, cnt, nfail, st);
+    if (rc) return rc;
   }
   // ---- 2. the whole gallery against the thresholds
   {
@@ -1294,6 +1316,15 @@ extern "C" int slic_cosine_topk(const float* Qn, int Nq, const float* Gn, int Ng
   SlicCarver w(workspace);
   return topk_search<false>(Qn, Nq, Gn, Ng, D, k, self_mask, out_idx, out_dist, nullptr, w, S_(stream));
 }
+
+// Where the bf16 candidate pass is on without SLIC_TOPK_BF16=1: where it measured ahead of the fp32 path by more than that path's own
+// run-to-run spread, on flat Gaussian rows (profiles/topk_bf16.txt: 10k x 100k at D = 128 / 256 / 512, k = 1 / 16 / 50: 0.25 - 0.61 of the
+// fp32 time).  Not at k = 88 (0.71 - 0.79: the candidates come close to their slots, a handful of queries fall back and cost a streaming
+// launch of their own; 2.2 x at 1k queries).  The choice cannot see the DATA: on a gallery of tight clusters (more rows within eps of a
+// query's k-th neighbour than a query has slots) every query falls back and the call costs the fp32 streaming search plus the bf16
+// pass, 1.3 - 2.0 x the fp32 time at these shapes.
+#define TKB_MEASURED_ON(Nq, Ng, D, k) ((int64_t)(Nq) * (Ng) >= 1000000000ll && (D) >= 128 && (k) <= 50)
+#include "topk_bf16.h"
 
 extern "C" int slic_topk_merge_lists(const float* pdist, const int32_t* pidx, int W, int Nq, int k, int32_t* out_idx,
                                      float* out_dist, void* stream) {

@@ -18,6 +18,7 @@ recomputes the winners' distances directly (LOSS.DIST_METRIC 'euclidean').  Plot
 are out of scope.
 """
 import ctypes
+import functools
 import json
 import os
 
@@ -26,6 +27,22 @@ import torch
 
 from . import _lib
 from ._lib import SlicConvArgs, call, ptr, stream
+
+
+def __getattr__(name):
+    # TOPK_BF16_EPS: the proven bound of |bf16 coarse score - fp32 score| the certified search lowers its thresholds by.  The library's
+    # constant is the only copy (slic_cosine_topk_bf16_eps), read when somebody asks for it.
+    if name == "TOPK_BF16_EPS":
+        return float(_lib.load().slic_cosine_topk_bf16_eps())
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))
+
+
+_PRECISIONS = ("fp32", "bf16")
+
+
+def _check_precision(precision):
+    if precision not in _PRECISIONS:
+        raise ValueError("precision must be 'fp32' or 'bf16', not %r" % (precision,))
 
 
 def _dev(x):
@@ -48,11 +65,15 @@ def _normalize(x, Dp):
     return out
 
 
-def cosine_topk_sharded(queries, gallery_shard, k, process_group, row_offset=None):
+def cosine_topk_sharded(queries, gallery_shard, k, process_group, row_offset=None, *, precision="fp32"):
     """Gallery sharded by rows across the ranks of `process_group` (queries replicated): every rank searches its
     shard, the [Nq, k] lists are all-gathered (RCCL) and merged on every GPU.  Returned indices are GLOBAL gallery
-    rows (rank order == row order unless `row_offset` is given)."""
-    return _topk_sharded(cosine_topk, queries, gallery_shard, k, process_group, row_offset)
+    rows (rank order == row order unless `row_offset` is given).  precision: as cosine_topk, for every shard's search."""
+    _check_precision(precision)
+
+    def search(q, g, k):
+        return cosine_topk(q, g, k=k, precision=precision)
+    return _topk_sharded(search, queries, gallery_shard, k, process_group, row_offset)
 
 
 def euclidean_topk_sharded(queries, gallery_shard, k, process_group, row_offset=None):
@@ -87,9 +108,16 @@ def _topk_sharded(search, queries, gallery_shard, k, process_group, row_offset):
     return out_i, out_d
 
 
-def cosine_topk(queries, gallery=None, k=20):
+def cosine_topk(queries, gallery=None, k=20, *, precision="fp32", info=None):
     """indices [Nq, k] (int32) and cosine distances [Nq, k] of the k nearest gallery rows, ascending;
-    gallery=None searches the queries themselves with the diagonal excluded (evaluate.py:221-222)."""
+    gallery=None searches the queries themselves with the diagonal excluded (evaluate.py:221-222).
+
+    precision="bf16": the similarity GEMM runs on the bf16 MFMA as a candidate pass and the result is still the exact top-k — the
+    candidates are rescored from the fp32 rows and a per-query certificate (TOPK_BF16_EPS, csrc/topk_bf16.h) decides whether they hold
+    the true k best; queries it does not cover are redone by the fp32 kernels.  The library takes the bf16 pass where it measured
+    faster (slic_cosine_topk_bf16_plan; SLIC_TOPK_BF16=1 forces it) and the fp32 search elsewhere.  info: a dict that receives
+    fallback_queries, overflow_queries, candidates, eps and path ("bf16" / "fp32") — one small device-to-host read, only when asked for."""
+    _check_precision(precision)
     lib = _lib.load()
     q = _dev(queries)
     self_mask = gallery is None
@@ -101,14 +129,32 @@ def cosine_topk(queries, gallery=None, k=20):
     Nq, Ng = qn.shape[0], gn.shape[0]
     idx = torch.empty(Nq, k, dtype=torch.int32, device=q.device)
     dist = torch.empty(Nq, k, dtype=torch.float32, device=q.device)
+    if precision == "bf16":
+        stats = torch.zeros(3, dtype=torch.int32, device=q.device) if info is not None else None
+        ws = _lib.workspace(lib.slic_cosine_topk_bf16_workspace_bytes(Nq, Ng, Dp, k), q.device, "topk")
+        call("slic_cosine_topk_bf16", ptr(qn), Nq, ptr(gn), Ng, Dp, k, int(self_mask), ptr(idx), ptr(dist), ptr(stats), ptr(ws), stream())
+        if info is not None:
+            plan = (ctypes.c_int * 6)()
+            call("slic_cosine_topk_bf16_plan", Nq, Ng, Dp, k, plan)
+            st = stats.tolist()
+            info.update(fallback_queries=st[0], overflow_queries=st[1], candidates=st[2], eps=float(lib.slic_cosine_topk_bf16_eps()),
+                        path="bf16" if plan[0] else "fp32")
+        return idx, dist
     ws = _lib.workspace(lib.slic_cosine_topk_workspace_bytes(Nq, Ng, k), q.device, "topk")
     call("slic_cosine_topk", ptr(qn), Nq, ptr(gn), Ng, Dp, k, int(self_mask), ptr(idx), ptr(dist), ptr(ws), stream())
+    if info is not None:
+        info.update(fallback_queries=0, overflow_queries=0, candidates=0, eps=float(lib.slic_cosine_topk_bf16_eps()), path="fp32")
     return idx, dist
 
 
-def euclidean_topk(queries, gallery=None, k=20):
+def euclidean_topk(queries, gallery=None, k=20, *, precision="fp32"):
     """indices [Nq, k] (int32) and euclidean distances [Nq, k] of the k nearest gallery rows, ascending (ties ->
-    lower index); gallery=None searches the queries themselves with the diagonal excluded, as cosine_topk does."""
+    lower index); gallery=None searches the queries themselves with the diagonal excluded, as cosine_topk does.
+    precision: 'fp32' only.  The certified bf16 candidate search of cosine_topk rests on unit rows; for raw rows the error bound of a
+    bf16 score scales with |q| |g|, so there is no fixed eps to certify with: precision='bf16' raises ValueError."""
+    _check_precision(precision)
+    if precision != "fp32":
+        raise ValueError("euclidean_topk: precision=%r is not supported (the bf16 candidate search needs unit rows)" % (precision,))
     lib = _lib.load()
     q = _dev(queries)
     self_mask = gallery is None
@@ -124,11 +170,12 @@ def euclidean_topk(queries, gallery=None, k=20):
     return idx, dist
 
 
-def _topk_search(dist_metric):
+def _topk_search(dist_metric, precision="fp32"):
+    _check_precision(precision)
     if dist_metric == 'cosine':
-        return cosine_topk
+        return cosine_topk if precision == "fp32" else functools.partial(cosine_topk, precision=precision)
     if dist_metric == 'euclidean':
-        return euclidean_topk
+        return euclidean_topk if precision == "fp32" else functools.partial(euclidean_topk, precision=precision)
     raise ValueError("dist_metric must be 'cosine' or 'euclidean', not %r" % (dist_metric,))
 
 
@@ -198,9 +245,9 @@ def get_topk_acc(distance_matrix, x_labels, y_labels=None, top_ks=[1, 5, 10, 20]
 
 
 def get_topk_acc_from_embeddings(x_embeddings, x_labels, y_embeddings=None, y_labels=None, top_ks=[1, 5, 10, 20],
-                                 dist_metric='cosine'):
-    """the same accuracies without the matrix: fused GEMM + top-k on the device ('cosine' or 'euclidean')"""
-    idx, _ = _topk_search(dist_metric)(x_embeddings, y_embeddings, k=top_ks[-1])
+                                 dist_metric='cosine', *, precision="fp32"):
+    """the same accuracies without the matrix: fused GEMM + top-k on the device ('cosine' or 'euclidean'; precision: see cosine_topk)"""
+    idx, _ = _topk_search(dist_metric, precision)(x_embeddings, y_embeddings, k=top_ks[-1])
     if y_labels is None:
         y_labels = x_labels
     return _acc_from_indices(idx.cpu().numpy(), x_labels, y_labels, top_ks)
@@ -228,12 +275,14 @@ def _label_hits(idx, q_labels, g_labels, top_ks, first_hit=None):
 
 
 def topk_acc_device(x_embeddings, x_labels, y_embeddings=None, y_labels=None, top_ks=[1, 5, 10, 20], dist_metric='cosine', *,
-                    kernels=None):
+                    kernels=None, precision="fp32"):
     """the value get_topk_acc returns (np.ndarray[len(top_ks)], float64) with the search AND the counting on the device: top-k
     search + slic_topk_label_hits, one small read-back of len(top_ks) integers.  Labels: lists, arrays or tensors.
-    kernels: a provider with topk / label_hits (validation.HipValidationKernels' interface) instead of the device."""
+    kernels: a provider with topk / label_hits (validation.HipValidationKernels' interface) instead of the device.
+    precision: see cosine_topk (the device search only; a provider keeps its own)."""
+    _check_precision(precision)
     if kernels is None:
-        idx, _ = _topk_search(dist_metric)(x_embeddings, y_embeddings, k=top_ks[-1])
+        idx, _ = _topk_search(dist_metric, precision)(x_embeddings, y_embeddings, k=top_ks[-1])
         hits = _label_hits(idx, x_labels, x_labels if y_labels is None else y_labels, top_ks)
     else:
         idx = kernels.topk(x_embeddings, y_embeddings, top_ks[-1], dist_metric)
@@ -273,12 +322,12 @@ def k_nearest_embeddings(args, model, cuda, device, train_loader, test_loader, t
 
 
 def topk_retrieval(args=None, X_train=None, y_train=None, X_test=None, y_test=None, ks=(1, 5, 10, 20, 50),
-                   dist_metric='cosine'):
+                   dist_metric='cosine', *, precision="fp32"):
     """iic_retrieve_clips.py:275-314.  Either `args.feature_dir` holds {train,test}_{feature,class}.npy
     ([V, 10, D] features averaged over the 10 clips, :280,287) or arrays are passed directly.
     Returns {k: correct}; writes topk_correct.json next to the features like the reference.
-    dist_metric: 'cosine' (the reference's) or 'euclidean'."""
-    search = _topk_search(dist_metric)
+    dist_metric: 'cosine' (the reference's) or 'euclidean'; precision: see cosine_topk."""
+    search = _topk_search(dist_metric, precision)
     feature_dir = getattr(args, "feature_dir", None) if args is not None else None
     if feature_dir is not None:
         X_train = np.load(os.path.join(feature_dir, 'train_feature.npy'))
