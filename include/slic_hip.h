@@ -150,6 +150,43 @@ int slic_kmeans_lloyd_global(const void* parts, int parts_f64, int64_t stride, i
                              float* sums, float* counts, float* C_new, float* Cp_new, float* cnorm_new, float* shift,
                              int spherical, double* status, void* stream);
 
+/* The certified bf16 E-step: the score GEMM runs on the bf16 MFMA over round-to-nearest-even images of the rows and
+ * only NOMINATES centroids — those whose coarse score minus its proven error bound is not above the smallest coarse score plus bound;
+ * a row with several nominees takes the argmin of their exact scores (the fmaf chain of slic_kmeans_assign, natural column order,
+ * first index wins).  Labels, n_changed and everything downstream are bit-identical to the fp32 entry points; the bf16 scores never
+ * reach an output (there is no best_score: callers that want one use slic_kmeans_assign).
+ * Domain: D % 8 == 0, D <= 512, N < 2^31; outside it these calls return SLIC_EINVAL with a message — they never switch precision.
+ *   slic_kmeans_bf16_plan : host only.  out[6] = {inside the domain (0 / 1), columns of an image row (D rounded up to 16), pair slots
+ *       per (row, 128-centroid block), 128-centroid blocks, bytes of the image of N rows, bytes of the image of K rows}.
+ *   slic_kmeans_bf16_eps  : the relative bound of |bf16-MFMA dot - fp32 dot| / (||x|| ||c||), the constant of slic_cosine_topk_bf16_eps.
+ *   slic_kmeans_bf16_image: image[N][Dp] (bf16, dense rows, zero padding) of X[N][D] (rows ldx floats apart) and, when norms is not
+ *       NULL, norms[i] = ||x_i||.  The image and norms of the centred data are made once per fit.
+ *   slic_kmeans_assign_bf16: labels of X against C (natural column order, NOT the k8-permuted copies) from the images Xb / Cb, the row
+ *       norms and cnorm (slic_kmeans_cnorm of C).  labels_old / n_changed as slic_kmeans_assign (*n_changed is added to).
+ *       stats (or NULL): int32[3] on the device, ADDED to: {rows whose label came from exact rescoring, rows among them whose slots
+ *       overflowed and that ran the exact chain over all K centroids, nominees of all rows (K for an overflowed row)}.
+ *   slic_kmeans_lloyd_step_bf16 / slic_kmeans_lloyd_local_bf16: slic_kmeans_lloyd_step / slic_kmeans_lloyd_local with this E-step inside.
+ *       Cb is SCRATCH of K x Dp bf16 values: the call writes C_old's image there.  The M-step, the payload layout and
+ *       slic_kmeans_lloyd_global are unchanged. */
+int slic_kmeans_bf16_plan(int64_t N, int K, int D, int64_t* out /* [6] */);
+float slic_kmeans_bf16_eps(void);
+int slic_kmeans_bf16_image(const float* X, int64_t N, int D, int ldx, void* image, float* norms, void* stream);
+size_t slic_kmeans_assign_bf16_workspace_bytes(int64_t N, int K);
+int slic_kmeans_assign_bf16(const float* X, const void* Xb, const float* xnorm, int64_t N, int D, int ldx, const float* C,
+                            const void* Cb, const float* cnorm, int K, int ldc, int32_t* labels, const int32_t* labels_old,
+                            int32_t* n_changed, int32_t* stats, void* workspace, void* stream);
+size_t slic_kmeans_lloyd_step_bf16_workspace_bytes(int64_t N, int K);
+int slic_kmeans_lloyd_step_bf16(const float* X, const float* Xp, const void* Xb, const float* xnorm, int64_t N, int D, int ldx,
+                                const float* C_old, void* Cb, const float* cnorm_old, int K, int32_t* labels,
+                                const int32_t* labels_old, int32_t* n_changed, float* sums, float* counts, float* C_new,
+                                float* Cp_new, float* cnorm_new, float* shift, int spherical, double* status, int32_t* stats,
+                                void* workspace, void* stream);
+size_t slic_kmeans_lloyd_local_bf16_workspace_bytes(int64_t N, int K);
+int slic_kmeans_lloyd_local_bf16(const float* X, const float* Xp, const void* Xb, const float* xnorm, int64_t N, int D, int ldx,
+                                 const float* C_old, void* Cb, const float* cnorm_old, int K, int32_t* labels,
+                                 const int32_t* labels_old, void* payload, int payload_f64, int32_t* stats, void* workspace,
+                                 void* stream);
+
 /* The collective of the sharded iteration behind the C ABI: an opaque RCCL communicator, created and destroyed explicitly (the
  * library's only global state besides the last-error string), and an in-place sum all-reduce on the caller's stream — a thin wrapper
  * over ncclAllReduce (RCCL over xGMI; bound at first use with dlopen, no link-time dependency).  One process per GPU: rank 0 calls

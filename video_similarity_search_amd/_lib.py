@@ -37,6 +37,16 @@ SIGNATURES = {
     "slic_kmeans_lloyd_local_workspace_bytes": (c_size_t, [L, I]),
     "slic_kmeans_lloyd_local": (I, [P, P, L, I, I, P, P, I, P, P, P, I, P, P]),
     "slic_kmeans_lloyd_global": (I, [P, I, L, I, P, I, I, P, P, P, P, P, P, I, P, P]),
+    # k-means, certified bf16 E-step
+    "slic_kmeans_bf16_plan": (I, [L, I, I, P]),
+    "slic_kmeans_bf16_eps": (F, []),
+    "slic_kmeans_bf16_image": (I, [P, L, I, I, P, P, P]),
+    "slic_kmeans_assign_bf16_workspace_bytes": (c_size_t, [L, I]),
+    "slic_kmeans_assign_bf16": (I, [P, P, P, L, I, I, P, P, P, I, I, P, P, P, P, P, P]),
+    "slic_kmeans_lloyd_step_bf16_workspace_bytes": (c_size_t, [L, I]),
+    "slic_kmeans_lloyd_step_bf16": (I, [P, P, P, P, L, I, I, P, P, P, I, P, P, P, P, P, P, P, P, P, I, P, P, P, P]),
+    "slic_kmeans_lloyd_local_bf16_workspace_bytes": (c_size_t, [L, I]),
+    "slic_kmeans_lloyd_local_bf16": (I, [P, P, P, P, L, I, I, P, P, P, I, P, P, P, I, P, P, P]),
     "slic_comm_unique_id": (I, [P]),
     "slic_comm_create": (I, [P, I, I, P]),
     "slic_comm_create_timeout": (I, [P, I, I, I, P]),

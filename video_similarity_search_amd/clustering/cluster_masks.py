@@ -44,7 +44,7 @@ def preprocess_features_kmeans(data, kernels=None):
 
 def fit_cluster(embeddings, method='Agglomerative', k=1000, l2normalize=True, finch_partition=0,
                 n_init=10, init='k-means++', process_group=None, random_state=None, kernels=None, exchange=None,
-                *, eps=0.14, min_samples=2, distance_threshold=None):
+                *, eps=0.14, min_samples=2, distance_threshold=None, precision=None):
     """Reference signature + keyword-only extras (n_init / init / process_group / random_state / kernels / exchange / eps /
     min_samples) that default to the reference's behaviour: KMeans(n_clusters=k, n_init=10).fit(embeddings).labels_, and for
     method='DBSCAN' DBSCAN(eps=0.14, min_samples=2, metric='cosine').fit(embeddings).labels_ (noise = -1; l2normalize does not
@@ -55,9 +55,12 @@ def fit_cluster(embeddings, method='Agglomerative', k=1000, l2normalize=True, fi
     ucf train", cluster_masks.py:52): the caller states it; without it the method raises NotImplementedError.
     process_group: `embeddings` is this rank's row shard (rank order == row order), the returned labels are this rank's.
     exchange: the sharded Lloyd iteration's one collective — 'allreduce' (RCCL through torch.distributed; the default), 'allgather', or
-    'oneshot' (the library's one-shot all-to-all over peer-mapped memory, csrc/oneshot.hip); None reads SLIC_KMEANS_EXCHANGE."""
+    'oneshot' (the library's one-shot all-to-all over peer-mapped memory, csrc/oneshot.hip); None reads SLIC_KMEANS_EXCHANGE.
+    precision ('kmeans' / 'spherical_kmeans'): 'fp32', 'bf16' (the certified bf16 E-step: the same labels) or None, see KMeans."""
 
     assert (method in _METHODS)
+    if precision not in (None, "fp32", "bf16"):
+        raise ValueError(f"precision={precision!r}: 'fp32' or 'bf16'")
     print("Clustering with {}...".format(method))
     if method == 'finch':
         # cluster_masks.py:79-86: FINCH(embeddings, distance='cosine'), take partition `finch_partition`
@@ -90,14 +93,14 @@ def fit_cluster(embeddings, method='Agglomerative', k=1000, l2normalize=True, fi
         print('clustering with spherical kmeans with k={}'.format(k))
         print(tuple(x.shape))
         km = KMeans(n_clusters=k, n_init=n_init, init=init, process_group=process_group, random_state=random_state,
-                    spherical=True, kernels=kernels, exchange=exchange).fit(x)
+                    spherical=True, kernels=kernels, exchange=exchange, precision=precision).fit(x)
     else:
         x = _to_device(embeddings) if kernels is None else kernels.to_device(embeddings)
         print("k:", k)
         if l2normalize:
             x = preprocess_features_kmeans(x, kernels)
         km = KMeans(n_clusters=k, n_init=n_init, init=init, process_group=process_group,
-                    random_state=random_state, kernels=kernels, exchange=exchange).fit(x)
+                    random_state=random_state, kernels=kernels, exchange=exchange, precision=precision).fit(x)
     labels = km.labels_
     print(labels.shape)
     n_clusters = len(set(labels.tolist())) - (1 if -1 in labels else 0)

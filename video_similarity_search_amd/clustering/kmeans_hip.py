@@ -21,6 +21,10 @@ Multi-GPU: pass `process_group`; X is then this rank's contiguo
     exchange='allgather': ONE all-gather of the fp32 payloads, added in rank order on every GPU; equals the oracle
         run with n_shards = world (== sklearn's per-thread buffers reduced in thread order);
     slic_kmeans_lloyd_global : combine + averaging + shift + next norms + status word.
+
+precision="bf16" (DESIGN.md §7f): the E-step of every iteration, sharded or not, and the final relabelling run as a certified bf16
+candidate pass with exact rescoring (slic_kmeans_lloyd_step_bf16 / _lloyd_local_bf16 / _assign_bf16) — the same labels to the bit.  The
+bf16 image and the norms of the centred rows are made once per fit; its three counters are read once, after the fit (bf16_stats_).
 """
 import ctypes
 import os
@@ -104,6 +108,43 @@ class HipKernels:
         ws = _lib.workspace(_lib.load().slic_kmeans_lloyd_local_workspace_bytes(N, K), X.device, "km_step")
         call("slic_kmeans_lloyd_local", ptr(X), ptr(Xp), N, Dp, X.stride(0), ptr(Cp_old), ptr(cnorm_old), K, ptr(labels),
              ptr(labels_old), ptr(payload), int(payload.dtype == torch.float64), ptr(ws), stream())
+
+    # ---- the certified bf16 E-step (include/slic_hip.h: slic_kmeans_*_bf16): same labels as the calls above
+    def bf16_image(self, X, want_norms=False):
+        """-> (bf16 image [N, Dp] of the rows as an int16 tensor, ||x_i|| or None)"""
+        N, D = X.shape
+        Dp = (D + 15) // 16 * 16
+        img = torch.empty(N, Dp, dtype=torch.int16, device=X.device)
+        norms = torch.empty(N, dtype=torch.float32, device=X.device) if want_norms else None
+        call("slic_kmeans_bf16_image", ptr(X), N, D, X.stride(0), ptr(img), ptr(norms), stream())
+        return img, norms
+
+    def assign_bf16(self, X, Xb, xnorm, C, Cb, cnorm, labels, labels_old, n_changed, stats):
+        N, Dp = X.shape
+        K = C.shape[0]
+        ws = _lib.workspace(_lib.load().slic_kmeans_assign_bf16_workspace_bytes(N, K), X.device, "km_assign_bf16")
+        call("slic_kmeans_assign_bf16", ptr(X), ptr(Xb), ptr(xnorm), N, Dp, X.stride(0), ptr(C), ptr(Cb), ptr(cnorm), K, C.stride(0),
+             ptr(labels), ptr(labels_old), ptr(n_changed), ptr(stats), ptr(ws), stream())
+
+    def lloyd_step_bf16(self, X, Xp, Xb, xnorm, C_old, Cb, cnorm_old, labels, labels_old, n_changed, sums, counts, C_new, Cp_new,
+                        cnorm_new, shift, status, stats, spherical=False):
+        """lloyd_step with the bf16 E-step inside; Cb is scratch for C_old's image"""
+        N, Dp = X.shape
+        K = C_old.shape[0]
+        assert X.stride(0) == Xp.stride(0) and C_old.is_contiguous() and C_new.is_contiguous()
+        ws = _lib.workspace(_lib.load().slic_kmeans_lloyd_step_bf16_workspace_bytes(N, K), X.device, "km_step_bf16")
+        call("slic_kmeans_lloyd_step_bf16", ptr(X), ptr(Xp), ptr(Xb), ptr(xnorm), N, Dp, X.stride(0), ptr(C_old), ptr(Cb), ptr(cnorm_old), K,
+             ptr(labels), ptr(labels_old), ptr(n_changed), ptr(sums), ptr(counts), ptr(C_new), ptr(Cp_new), ptr(cnorm_new),
+             ptr(shift), int(spherical), ptr(status), ptr(stats), ptr(ws), stream())
+
+    def lloyd_local_bf16(self, X, Xp, Xb, xnorm, C_old, Cb, cnorm_old, labels, labels_old, payload, stats):
+        """lloyd_local with the bf16 E-step inside"""
+        N, Dp = X.shape
+        K = C_old.shape[0]
+        assert X.stride(0) == Xp.stride(0) and C_old.is_contiguous() and payload.numel() == K * Dp + K + 2
+        ws = _lib.workspace(_lib.load().slic_kmeans_lloyd_local_bf16_workspace_bytes(N, K), X.device, "km_step_bf16")
+        call("slic_kmeans_lloyd_local_bf16", ptr(X), ptr(Xp), ptr(Xb), ptr(xnorm), N, Dp, X.stride(0), ptr(C_old), ptr(Cb), ptr(cnorm_old), K,
+             ptr(labels), ptr(labels_old), ptr(payload), int(payload.dtype == torch.float64), ptr(stats), ptr(ws), stream())
 
     def lloyd_global(self, parts, C_old, sums, counts, C_new, Cp_new, cnorm_new, shift, status, spherical=False):
         """sharded iteration, part 2 (after the collective): parts = [W, K*D + K + 2] gathered fp32 payloads or
@@ -320,7 +361,7 @@ class KMeans:
     copied to the current device)."""
 
     def __init__(self, n_clusters, n_init=10, max_iter=300, tol=1e-4, init="k-means++", random_state=None,
-                 process_group=None, fixed_iters=False, trace=False, kernels=None, spherical=False, exchange=None):
+                 process_group=None, fixed_iters=False, trace=False, kernels=None, spherical=False, exchange=None, precision=None):
         self.n_clusters = int(n_clusters)
         self.n_init = int(n_init)
         self.max_iter = int(max_iter)
@@ -337,6 +378,12 @@ class KMeans:
         assert exchange in ("allreduce", "allgather", "oneshot"), exchange
         self.exchange = exchange               # the sharded run's one collective per iteration (module docstring)
         self.k = kernels if kernels is not None else HipKernels()
+        # the E-step's arithmetic: 'fp32' (the MFMA chain itself) or 'bf16' (certified bf16 candidates + exact rescoring: the same labels,
+        # DESIGN.md §7f).  None: 'fp32', or — SLIC_KMEANS_BF16=1 — 'bf16' wherever the fit is inside that path's domain (D <= 512)
+        if precision not in (None, "fp32", "bf16"):
+            raise ValueError(f"precision={precision!r}: 'fp32' or 'bf16'")
+        self.precision = precision
+        self.bf16_stats_ = None
 
     # ------------------------------------------------------------------ helpers
     def _rng(self):
@@ -380,6 +427,8 @@ class KMeans:
     def fit(self, X):
         self._fit_rs = None
         self.init_indices_log_ = []
+        self._bf16 = self._use_bf16(int(np.shape(X)[1]))             # raises for precision='bf16' outside its domain: before any launch
+        self.bf16_stats_ = None
         self.k.check()
         X = self.k.to_device(X)
         N, D = X.shape
@@ -437,6 +486,7 @@ class KMeans:
             inits = [np.asarray(a, np.float32)]
         n_runs = self.n_init if inits is None else len(inits)
 
+        self._bf16_stats = torch.zeros(3, dtype=torch.int32, device=dev) if self._bf16 else None
         best = None
         seeded = self._kmeans_plusplus_all(Xc, K, n_runs) if (inits is None and n_runs > 1) else None
         for run in range(n_runs):
@@ -459,7 +509,22 @@ class KMeans:
         self.strict_ = best["strict"]
         self.n_relocations_ = best["n_relocations"]
         self.trace_ = best.get("trace")
+        if self._bf16:
+            st = self._bf16_stats.cpu().tolist()                    # read once per fit
+            self.bf16_stats_ = dict(rows_rescored=st[0], rows_overflowed=st[1], candidates=st[2])
         return self
+
+    def _use_bf16(self, D):
+        """does this fit run the certified bf16 E-step?  An explicit precision='bf16' outside the domain is an error, never a silent fp32 run"""
+        Dp = (D + 7) // 8 * 8
+        able = hasattr(self.k, "assign_bf16") and bool(getattr(self.k, "uses_perm", False))
+        if self.precision == "bf16":
+            if Dp > 512:
+                raise ValueError(f"precision='bf16' takes D <= 512 (D={D}); use precision='fp32'")
+            if not able:
+                raise ValueError("precision='bf16': this kernel provider has no bf16 E-step")
+            return True
+        return self.precision is None and os.environ.get("SLIC_KMEANS_BF16", "0") == "1" and Dp <= 512 and able
 
     # ------------------------------------------------------------------ one Lloyd run
     def _lloyd_single(self, Xc, C, tol_abs):
@@ -482,6 +547,11 @@ class KMeans:
             Cp = [torch.empty_like(C) for _ in range(3)]                                   # permuted twins of Cb
         else:
             Cp = [None] * 3
+        bf = bool(getattr(self, "_bf16", False))
+        if bf:
+            Xb, xnb = self._bf16_image(Xc)                                                 # once per fit, shared by the inits
+            Cimg = torch.empty(K, Xb.shape[1], dtype=torch.int16, device=dev)              # the centres' image: rewritten every iteration
+            bstats = self._bf16_stats
         n_changed = [torch.zeros(1, dtype=torch.int32, device=dev) for _ in range(2)]
         part = [torch.empty(K * Dp + K, dtype=torch.float32, device=dev) for _ in range(2)]   # [sums | counts]: the all-gather unit
         shift = torch.empty(K, dtype=torch.float32, device=dev)
@@ -547,6 +617,11 @@ class KMeans:
                 k.cnorm(Cin, cnorm[0])                             # later norms / permuted centres come out of finalize
                 if perm:
                     k.permute_k8(Cin, Cp[0])
+            if bf and perm and not self._sharded and hasattr(k, "lloyd_step_bf16"):
+                k.lloyd_step_bf16(Xc, Xp, Xb, xnb, Cin, Cimg, cnorm[it % 3], lab, lab_old, n_changed[sl], gsums[sl], gcounts[sl],
+                                  Cout, Cp[(it + 1) % 3], cnorm[(it + 1) % 3], shift, status[sl], bstats, **sph)
+                read_back(sl)
+                return
             if perm and not self._sharded and hasattr(k, "lloyd_step"):
                 k.lloyd_step(Xc, Xp, Cin, Cp[it % 3], cnorm[it % 3], lab, lab_old, n_changed[sl], gsums[sl], gcounts[sl],
                              Cout, Cp[(it + 1) % 3], cnorm[(it + 1) % 3], shift, status[sl], **sph)
@@ -559,7 +634,10 @@ class KMeans:
                 # where the loop reads that iteration's status; its peers see the poison in the same status word and raise there too.
                 if not local_failure:
                     try:
-                        k.lloyd_local(Xc, Xp if perm else None, Cin, Cp[it % 3], cnorm[it % 3], lab, lab_old, payload[sl])
+                        if bf:
+                            k.lloyd_local_bf16(Xc, Xp, Xb, xnb, Cin, Cimg, cnorm[it % 3], lab, lab_old, payload[sl], bstats)
+                        else:
+                            k.lloyd_local(Xc, Xp if perm else None, Cin, Cp[it % 3], cnorm[it % 3], lab, lab_old, payload[sl])
                     except Exception as e:                              # noqa: BLE001 — re-raised by read() of this iteration
                         local_failure.append((it, e))
                 if local_failure:
@@ -588,7 +666,9 @@ class KMeans:
                 read_back(sl)
                 return
             n_changed[sl].zero_()
-            if perm:
+            if bf:
+                k.assign_bf16(Xc, Xb, xnb, Cin, k.bf16_image(Cin)[0], cnorm[it % 3], lab, lab_old, n_changed[sl], bstats)
+            elif perm:
                 k.assign_perm(Xp, Cp[it % 3], cnorm[it % 3], lab, lab_old, n_changed[sl])
             else:
                 k.assign(Xc, Cin, cnorm[it % 3], lab, lab_old, n_changed[sl])
@@ -663,7 +743,9 @@ class KMeans:
             cn = cnorm[(last + 1) % 3] if self.max_iter > 0 else cnorm[0]
             if self.max_iter <= 0:
                 k.cnorm(C, cn)
-            if perm and self.max_iter > 0:
+            if bf:
+                k.assign_bf16(Xc, Xb, xnb, C, k.bf16_image(C)[0], cn, out, None, None, bstats)
+            elif perm and self.max_iter > 0:
                 k.assign_perm(Xp, Cp[(last + 1) % 3], cn, out, None, None)
             else:
                 k.assign(Xc, C, cn, out, None, None)
@@ -687,6 +769,13 @@ class KMeans:
             self.k.cnorm(Xc, xn)
             self._norm_key, self._norm_X = key, xn
         return self._norm_X
+
+    def _bf16_image(self, Xc):
+        """bf16 image and row norms of the (centred) data for the bf16 E-step; cached while Xc is the same tensor"""
+        key = (Xc.data_ptr(), tuple(Xc.shape), Xc._version)
+        if getattr(self, "_img_key", None) != key:
+            self._img_key, self._img = key, self.k.bf16_image(Xc, want_norms=True)
+        return self._img
 
     def _permuted(self, Xc):
         """k-permuted copy of the (centred) data for the LDS-DMA E-step; cached while Xc is the same tensor"""

@@ -2214,3 +2214,5 @@ extern "C" int slic_cumsum_search(const float* v, int64_t N, const double* vals,
   SLIC_LAUNCH_CHECK();
   return SLIC_OK;
 }
+
+#include "kmeans_bf16.h"   // the certified bf16 E-step: kernels and entry points (uses the launch helpers above)

@@ -16,34 +16,9 @@
 // Nothing here is approximate in its result: the bf16 scores never reach the output.
 #pragma once
 
-#define TK_BF16_EPS 0.008f    // proven bound of |bf16-MFMA score - fp32 score| for L2-normalised rows, D <= 512
+#include "bf16_image.h"      // TK_BF16_EPS, tkb_round_bf16, tkb_convert: shared with the k-means E-step
+
 #define TKB_PC 32             // pending candidates per lane between drains
-
-typedef __bf16 tkb_bf16x8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ unsigned tkb_round_bf16(float x) {
-  const unsigned u = __float_as_uint(x);
-  if ((u & 0x7FFFFFFFu) > 0x7F800000u) return 0x7FC0u;                          // NaN stays NaN
-  return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;                                // round to nearest, ties to even
-}
-
-// one thread per 16-byte chunk of the image: 8 consecutive columns of a row (D % 8 == 0: a chunk is inside the row or in the padding)
-__global__ __launch_bounds__(256) void tkb_convert(const float* __restrict__ X, int64_t N, int D, int Dp, uint4* __restrict__ out) {
-  const int cpr = Dp >> 3;
-  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (e >= N * cpr) return;
-  const int64_t row = e / cpr;
-  const int c = (int)(e - row * cpr) * 8;
-  uint4 o = {0u, 0u, 0u, 0u};
-  if (c < D) {
-    const f32x4 a = *(const f32x4*)(X + row * D + c), b = *(const f32x4*)(X + row * D + c + 4);
-    o.x = tkb_round_bf16(a[0]) | (tkb_round_bf16(a[1]) << 16);
-    o.y = tkb_round_bf16(a[2]) | (tkb_round_bf16(a[3]) << 16);
-    o.z = tkb_round_bf16(b[0]) | (tkb_round_bf16(b[1]) << 16);
-    o.w = tkb_round_bf16(b[2]) | (tkb_round_bf16(b[3]) << 16);
-  }
-  out[e] = o;
-}
 
 // The collect pass on the bf16 MFMA.  The operand path is the register-operand ring of mfma_ring.h, byte for byte: a ring stage is
 // 128 gallery rows x 128 BYTES — 64 bf16 columns instead of 32 floats — moved by the same DMAs into the same swizzled image, and the
@@ -323,11 +298,11 @@ extern "C" int slic_cosine_topk_bf16(const float* Qn, int Nq, const float* Gn, i
   if (rc1) return rc1;
   // ---- 2. the bf16 images
   const int cpr = p.Dp / 8;
-  tkb_convert<<<dim3((unsigned)slic_cdiv((int64_t)Ng * cpr, 256)), dim3(256), 0, st>>>(Gn, Ng, D, p.Dp, (uint4*)Gb);
+  tkb_convert<<<dim3((unsigned)slic_cdiv((int64_t)Ng * cpr, 256)), dim3(256), 0, st>>>(Gn, Ng, D, D, p.Dp, (uint4*)Gb);
   SLIC_LAUNCH_CHECK();
   if (same) Qb = Gb;
   else {
-    tkb_convert<<<dim3((unsigned)slic_cdiv((int64_t)Nq * cpr, 256)), dim3(256), 0, st>>>(Qn, Nq, D, p.Dp, (uint4*)Qb);
+    tkb_convert<<<dim3((unsigned)slic_cdiv((int64_t)Nq * cpr, 256)), dim3(256), 0, st>>>(Qn, Nq, D, D, p.Dp, (uint4*)Qb);
     SLIC_LAUNCH_CHECK();
   }
   // ---- 3. the whole gallery on the bf16 MFMA against tau - eps
