@@ -834,6 +834,26 @@ int slic_moco_ce_bwd(const float* q, const float* k, const float* memory, int B,
  * queue_label is given */
 int slic_moco_enqueue(float* memory, int64_t* queue_label, const float* k, const int64_t* k_label, int B, int K, int D, int index,
                       void* stream);
+/* The top-k accuracy of the same logits without writing them (online_train.py calc_mask_accuracy / calc_topk_accuracy against
+ * column 0).  Order the columns of row b by descending logit, ties by ascending column; best(b) = the first positive column in that
+ * order (positives as in slic_moco_ce_fwd), rank(b) = the number of columns ahead of it.  rank [B] (NULL = not wanted) =
+ * min(rank(b), top_ks[n_ks - 1]); hits[i] = #{b : rank(b) < top_ks[i]}, written, not accumulated.  top_ks is a HOST array of
+ * n_ks <= 8 ascending values in 1 .. 8; everything else lives on the device.  Integer results: two runs give the same bits.
+ * workspace: 8-byte aligned, SLIC_MOCO_TOPK_WORKSPACE_BYTES(B) bytes.  Limits and SLIC_EINVAL as slic_moco_ce_fwd. */
+#define SLIC_MOCO_TOPK_WORKSPACE_BYTES(B) ((size_t)(SLIC_MOCO_PARTS + 1) * (size_t)(B) * 8)
+int slic_moco_topk_hits(const float* q, const float* k, const float* memory, int B, int K, int D, float T, const int64_t* k_label,
+                        const int64_t* queue_label, const int32_t* top_ks, int n_ks, int32_t* rank, int32_t* hits, void* workspace,
+                        void* stream);
+/* The same definition on dense logits [B, C] (row pitch ld) and a dense mask [B, C] (uint8, non-zero = positive, row pitch ldm).
+ * rank [B] is not saturated; a row without a positive gets rank C and never hits.  top_ks: HOST, n_ks <= 8 ascending values in
+ * 1 .. C.  hits [n_ks] is written, not accumulated. */
+int slic_mask_topk_hits(const float* logits, int ld, const uint8_t* mask, int ldm, int B, int C, const int32_t* top_ks, int n_ks,
+                        int32_t* rank, int32_t* hits, void* stream);
+/* torch.nn.functional.normalize(x, dim=1, eps) of dense rows x [B, D] and its backward (models/infoNCE.py:164,177):
+ * y = x / max(||x||, eps); inv [B] = 1 / max(||x||, eps), negated for a row the eps clamped, is what the backward keeps.
+ * dx = |inv| (dy - y <dy, y>), and dx = dy / eps for a clamped row.  One wave per row, fixed summation order. */
+int slic_l2normalize_fwd(const float* x, int B, int D, float eps, float* y, float* inv, void* stream);
+int slic_l2normalize_bwd(const float* dy, const float* y, const float* inv, int B, int D, float* dx, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Clip transforms (coclr_utils/transforms.py: crop, pad, flip, bilinear resize, brightness / contrast / saturation jitter, random

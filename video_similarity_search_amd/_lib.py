@@ -187,6 +187,10 @@ SIGNATURES = {
     "slic_moco_ce_fwd": (I, [P, P, P, I, I, I, F, P, P, P, P, P, P]),
     "slic_moco_ce_bwd": (I, [P, P, P, I, I, I, F, P, P, P, P, P, P, P]),
     "slic_moco_enqueue": (I, [P, P, P, P, I, I, I, I, P]),
+    "slic_moco_topk_hits": (I, [P, P, P, I, I, I, F, P, P, P, I, P, P, P, P]),
+    "slic_mask_topk_hits": (I, [P, I, P, I, I, I, P, I, P, P, P]),
+    "slic_l2normalize_fwd": (I, [P, I, I, F, P, P, P]),
+    "slic_l2normalize_bwd": (I, [P, P, P, I, I, P, P]),
     # clip transforms
     "slic_clip_transform_workspace_bytes": (c_size_t, [I, I, I, I]),
     "slic_clip_transform_stats": (I, [P, P, c_size_t, I, I, I, I, I, P, P]),

@@ -18,13 +18,26 @@
 //    the scale.
 // The fused step holds no [B, K] and no [K, D] temporary: its workspace is SLIC_MOCO_PARTS records per query and SLIC_MOCO_DQ_PARTS
 // partial gradients.
+//
+// Rank of the best positive (slic_moco_topk_hits: the top-k accuracy of the step) runs on the same two engines as two more epilogues,
+// two sweeps over the queue: BEST keeps the lane's first positive column in (descending logit, ascending column) order, COUNT counts
+// the columns ahead of the row's winner.  Both sweeps form the same accumulators in the same order, so a logit has the same bits in
+// both; the records are (float, int) pairs and integer counts, merged in any order with the same result.  Without labels column 0 is
+// the only positive and the first sweep is not run.
+#include <limits.h>
 #include <math.h>
+#include <type_traits>
 #include "mfma_ring.h"
 
 #define MOCO_BG 128                    // queue rows per tile
 #define MOCO_CS_LD 33                  // row pitch of the coefficient tile in LDS (32 queries + 1: the transposing fill stays conflict-free)
 
-enum { MOCO_LOGITS = 0, MOCO_CE = 1, MOCO_CE_BWD = 2, MOCO_LOGITS_BWD = 3 };
+enum { MOCO_LOGITS = 0, MOCO_CE = 1, MOCO_CE_BWD = 2, MOCO_LOGITS_BWD = 3, MOCO_BEST = 4, MOCO_COUNT = 5 };
+
+// a column of the logit matrix as the rank orders them: descending logit, ties by ascending column.  v: the logit's bits
+struct MocoCol { float v; int c; };
+static_assert(sizeof(MocoCol) == 8, "one 8-byte record");
+__device__ __forceinline__ bool moco_ahead(float v, int c, float v2, int c2) { return v > v2 || (v == v2 && c < c2); }
 
 // queue row of accumulator register v, relative to the lane's first one (MFMA 32x32 output layout)
 __device__ __forceinline__ int moco_vrow(int v) { return (v & 3) + 8 * (v >> 2); }
@@ -79,6 +92,34 @@ __device__ __forceinline__ void moco_store_logits(const f32x16& a, float T, int 
   }
 }
 
+// rank, first sweep (BEST): the first of the lane's positive queue columns 1 + g in rank order
+__device__ __forceinline__ void moco_best_accum(const f32x16& a, float T, int gl, int gend, int64_t lq, const int64_t* __restrict__ qlab,
+                                                float& bv, int& bc) {
+#pragma unroll
+  for (int v = 0; v < 16; ++v) {
+    const int g = gl + moco_vrow(v);
+    if (g < gend && moco_is_pos(qlab[g], lq)) {
+      const float x = a[v] / T;
+      if (moco_ahead(x, g + 1, bv, bc)) { bv = x; bc = g + 1; }
+    }
+  }
+}
+
+// rank, second sweep (COUNT): how many of the sixteen columns come before column tc with logit tv
+__device__ __forceinline__ void moco_count_accum(const f32x16& a, float T, int gl, int gend, float tv, int tc, int& cnt) {
+#pragma unroll
+  for (int v = 0; v < 16; ++v) {
+    const int g = gl + moco_vrow(v);
+    cnt += (g < gend && moco_ahead(a[v] / T, g + 1, tv, tc)) ? 1 : 0;
+  }
+}
+
+__device__ __forceinline__ void moco_best_merge_halves(float& bv, int& bc) {
+  const float v2 = __shfl_xor(bv, 32);
+  const int c2 = __shfl_xor(bc, 32);
+  if (moco_ahead(v2, c2, bv, bc)) { bv = v2; bc = c2; }
+}
+
 // both lane halves hold records of the same query: merge into both
 __device__ __forceinline__ void moco_merge_halves(float& m, float& s, float& ps, float& pc) {
   const float m2 = __shfl_xor(m, 32), s2 = __shfl_xor(s, 32), ps2 = __shfl_xor(ps, 32), pc2 = __shfl_xor(pc, 32);
@@ -97,7 +138,8 @@ template <int NK, int MODE, bool LAB>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void moco_ring(
     const float* __restrict__ Q, int B, const float* __restrict__ Mem, int K, int D, float T, int per,
     float* __restrict__ out /* LOGITS: [B][K + 1] */, f32x4* __restrict__ part /* CE: [slices][B] (max, sum-exp, pos sum, pos count) */,
-    const int64_t* __restrict__ klab, const int64_t* __restrict__ qlab) {
+    const int64_t* __restrict__ klab, const int64_t* __restrict__ qlab,
+    const MocoCol* __restrict__ thr /* COUNT: [B] the column to rank */, MocoCol* __restrict__ rpart /* BEST / COUNT: [slices][B] */) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   static_assert(NK % 4 == 0, "a queue tile is a whole number of ring turns");
   const int tid = threadIdx.x, lane = tid & 63;
@@ -124,6 +166,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   if constexpr (LAB) lq = q < B ? klab[q] : -1;
   float* orow = nullptr;
   if constexpr (MODE == MOCO_LOGITS) orow = out + (int64_t)(q < B ? q : 0) * (K + 1) + 1;
+  float bv = -INFINITY;                                        // BEST: the running best positive; COUNT: the column to rank
+  int bc = INT_MAX, cnt = 0;
+  if constexpr (MODE == MOCO_COUNT) {
+    const MocoCol t = thr[q < B ? q : B - 1];
+    bv = t.v; bc = t.c;
+  }
   f32x16 acc[4];
   f32x4 a[2][4];
   slic_rt_ring_prime<4>(a, lds, r, h, [&](int kn) SLIC_RT_INLINE { issue(0, kn); });
@@ -141,6 +189,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     for (int ct = 0; ct < 4; ++ct) {
       if constexpr (MODE == MOCO_LOGITS) {
         if (q < B) moco_store_logits(acc[ct], T, gl + 32 * ct, gend, orow);
+      } else if constexpr (MODE == MOCO_BEST) {
+        moco_best_accum(acc[ct], T, gl + 32 * ct, gend, lq, qlab, bv, bc);
+      } else if constexpr (MODE == MOCO_COUNT) {
+        moco_count_accum(acc[ct], T, gl + 32 * ct, gend, bv, bc, cnt);
       } else {
         moco_ce_accum<LAB>(acc[ct], T, gl + 32 * ct, gend, lq, qlab, m, s, ps, pc);
       }
@@ -152,6 +204,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
       const f32x4 rec = {m, s, ps, pc};
       part[(int64_t)blockIdx.y * B + q] = rec;
     }
+  }
+  if constexpr (MODE == MOCO_BEST) {
+    moco_best_merge_halves(bv, bc);
+    if (h == 0 && q < B) rpart[(int64_t)blockIdx.y * B + q] = MocoCol{bv, bc};
+  }
+  if constexpr (MODE == MOCO_COUNT) {
+    cnt += __shfl_xor(cnt, 32);
+    if (h == 0 && q < B) rpart[(int64_t)blockIdx.y * B + q] = MocoCol{0.f, cnt};
   }
   slic_rt_wait<0>();                                           // the trailing all-zero DMAs must land before the workgroup leaves
 }
@@ -177,11 +237,13 @@ __global__ __launch_bounds__(256) void moco_tile32(
     float* __restrict__ out /* LOGITS: [B][K + 1] */, const float* __restrict__ dout /* LOGITS_BWD: [B][K + 1] */,
     f32x4* __restrict__ part /* CE */, const int64_t* __restrict__ klab, const int64_t* __restrict__ qlab,
     const float* __restrict__ lse, const float* __restrict__ npos /* CE_BWD: [B] each */,
-    float* __restrict__ dqpart /* backward: [slices][B][D] */) {
+    float* __restrict__ dqpart /* backward: [slices][B][D] */,
+    const MocoCol* __restrict__ thr /* COUNT: [B] */, MocoCol* __restrict__ rpart /* BEST / COUNT: [slices][B] */) {
   constexpr bool BWD = MODE == MOCO_CE_BWD || MODE == MOCO_LOGITS_BWD;
   constexpr int NDT = NK / 4;                                  // d-tiles of 32 columns per wave: d-tile w + 4 i
   __shared__ float cs[BWD ? MOCO_BG * MOCO_CS_LD : 1];         // c[row of the tile][query]
   __shared__ f32x4 wst[MODE == MOCO_CE ? 4 * 32 : 1];
+  __shared__ MocoCol rst[MODE == MOCO_BEST || MODE == MOCO_COUNT ? 4 * 32 : 1];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r = lane & 31, h = lane >> 5;
@@ -208,6 +270,12 @@ __global__ __launch_bounds__(256) void moco_tile32(
   }
   float* orow = nullptr;
   if constexpr (MODE == MOCO_LOGITS) orow = out + (int64_t)(qv ? q : 0) * (K + 1) + 1;
+  float bv = -INFINITY;                                        // BEST: the running best positive; COUNT: the column to rank
+  int bc = INT_MAX, cnt = 0;
+  if constexpr (MODE == MOCO_COUNT) {
+    const MocoCol t = thr[qv ? q : 0];
+    bv = t.v; bc = t.c;
+  }
   f32x16 dqacc[BWD ? NDT : 1];
   if constexpr (BWD) {
 #pragma unroll
@@ -237,6 +305,10 @@ __global__ __launch_bounds__(256) void moco_tile32(
         if (qv) moco_store_logits(acc, T, gl, gend, orow);
       } else if constexpr (MODE == MOCO_CE) {
         moco_ce_accum<LAB>(acc, T, gl, gend, lq, qlab, m, s, ps, pc);
+      } else if constexpr (MODE == MOCO_BEST) {
+        moco_best_accum(acc, T, gl, gend, lq, qlab, bv, bc);
+      } else if constexpr (MODE == MOCO_COUNT) {
+        moco_count_accum(acc, T, gl, gend, bv, bc, cnt);
       } else {
 #pragma unroll
         for (int v = 0; v < 16; ++v) {
@@ -295,6 +367,25 @@ __global__ __launch_bounds__(256) void moco_tile32(
       }
       const f32x4 rec = {tm, ts, tp, tc};
       part[(int64_t)blockIdx.y * B + q] = rec;
+    }
+  }
+  if constexpr (MODE == MOCO_BEST || MODE == MOCO_COUNT) {
+    if constexpr (MODE == MOCO_BEST) moco_best_merge_halves(bv, bc);
+    else cnt += __shfl_xor(cnt, 32);
+    if (h == 0) rst[wave * 32 + r] = MODE == MOCO_BEST ? MocoCol{bv, bc} : MocoCol{0.f, cnt};
+    __syncthreads();
+    if (wave == 0 && h == 0 && qv) {
+      MocoCol t = rst[r];
+#pragma unroll
+      for (int w = 1; w < 4; ++w) {
+        const MocoCol u = rst[w * 32 + r];
+        if constexpr (MODE == MOCO_BEST) {
+          if (moco_ahead(u.v, u.c, t.v, t.c)) t = u;
+        } else {
+          t.c += u.c;
+        }
+      }
+      rpart[(int64_t)blockIdx.y * B + q] = t;
     }
   }
   if constexpr (BWD) {
@@ -411,6 +502,137 @@ __global__ __launch_bounds__(256) void moco_enqueue(float* __restrict__ Mem, int
 }
 
 // ------------------------------------------------------------------------------------------
+// rank of the best positive
+// ------------------------------------------------------------------------------------------
+struct MocoTopKs { int n, k[8]; };
+
+// thr[b] = the first positive column of row b in rank order: column 0, or the best of the S per-slice records when it is strictly
+// larger (an equal logit loses to column 0, the lower column).  One wave per query
+__global__ __launch_bounds__(256) void moco_rank_thr(const float* __restrict__ Q, const float* __restrict__ Kk, int B, int D, float T,
+                                                     const MocoCol* __restrict__ best, int S, MocoCol* __restrict__ thr) {
+  const int lane = threadIdx.x & 63;
+  const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (b >= B) return;
+  const float l0 = moco_dot_wave(Q + (int64_t)b * D, Kk + (int64_t)b * D, D, lane) / T;
+  float bv = -INFINITY;
+  int bc = INT_MAX;
+  for (int sl = lane; sl < S; sl += 64) {
+    const MocoCol u = best[(int64_t)sl * B + b];
+    if (moco_ahead(u.v, u.c, bv, bc)) { bv = u.v; bc = u.c; }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float v2 = __shfl_xor(bv, o);
+    const int c2 = __shfl_xor(bc, o);
+    if (moco_ahead(v2, c2, bv, bc)) { bv = v2; bc = c2; }
+  }
+  if (lane == 0) thr[b] = moco_ahead(bv, bc, l0, 0) ? MocoCol{bv, bc} : MocoCol{l0, 0};
+}
+
+// hits[i] = the workgroup's sum of mine[i], i < ks.n: wave xor trees, then integer atomics in LDS.  Every thread of the workgroup calls it
+__device__ __forceinline__ void moco_hits_reduce(const int (&mine)[8], const MocoTopKs& ks, int* __restrict__ hits) {
+  __shared__ int sh[8];
+  if (threadIdx.x < 8) sh[threadIdx.x] = 0;
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    int x = mine[i];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
+    if ((threadIdx.x & 63) == 0 && x) atomicAdd(&sh[i], x);
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < ks.n) hits[threadIdx.x] = sh[threadIdx.x];
+}
+
+// rank[b] = min(kmax, columns ahead: the S slice counts added), hits[i] = #{b : rank[b] < k_i}.  One workgroup; integer sums
+__global__ __launch_bounds__(1024) void moco_rank_finish(const MocoCol* __restrict__ cnt, int S, int B, MocoTopKs ks, int* __restrict__ rank,
+                                                         int* __restrict__ hits) {
+  const int kmax = ks.k[ks.n - 1];
+  int mine[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  for (int b = threadIdx.x; b < B; b += 1024) {
+    int c = 0;
+    for (int sl = 0; sl < S; ++sl) c += cnt[(int64_t)sl * B + b].c;
+    c = c < kmax ? c : kmax;
+    if (rank) rank[b] = c;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) mine[i] += (i < ks.n && c < ks.k[i]) ? 1 : 0;
+  }
+  moco_hits_reduce(mine, ks, hits);
+}
+
+// dense logits [B, C] and mask [B, C]: one wave per row, two passes.  best = the first masked column in rank order, rank = the columns
+// ahead of it (C when the row has no masked column)
+__global__ __launch_bounds__(256) void mask_rank_rows(const float* __restrict__ X, int ld, const unsigned char* __restrict__ Msk, int ldm,
+                                                      int B, int C, int* __restrict__ rank) {
+  const int lane = threadIdx.x & 63;
+  const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (b >= B) return;
+  const float* x = X + (int64_t)b * ld;
+  const unsigned char* mk = Msk + (int64_t)b * ldm;
+  float bv = -INFINITY;
+  int bc = INT_MAX;
+  bool any = false;
+  for (int c = lane; c < C; c += 64)
+    if (mk[c]) {
+      const float v = x[c];
+      if (!any || moco_ahead(v, c, bv, bc)) { bv = v; bc = c; }
+      any = true;
+    }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float v2 = __shfl_xor(bv, o);
+    const int c2 = __shfl_xor(bc, o);
+    const bool a2 = __shfl_xor((int)any, o) != 0;
+    if (a2 && (!any || moco_ahead(v2, c2, bv, bc))) { bv = v2; bc = c2; }
+    any = any || a2;
+  }
+  int cnt = 0;
+  for (int c = lane; c < C; c += 64) cnt += moco_ahead(x[c], c, bv, bc) ? 1 : 0;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);
+  if (lane == 0) rank[b] = any ? cnt : C;
+}
+
+// hits[i] = #{b : rank[b] < k_i}; one workgroup
+__global__ __launch_bounds__(1024) void mask_rank_hits(const int* __restrict__ rank, int B, MocoTopKs ks, int* __restrict__ hits) {
+  int mine[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  for (int b = threadIdx.x; b < B; b += 1024) {
+    const int c = rank[b];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) mine[i] += (i < ks.n && c < ks.k[i]) ? 1 : 0;
+  }
+  moco_hits_reduce(mine, ks, hits);
+}
+
+// F.normalize(x, dim=1): y = x / max(||x||, eps), one wave per row; inv[b] = 1 / max(||x_b||, eps) is kept for the backward
+__global__ __launch_bounds__(256) void moco_l2norm_fwd(const float* __restrict__ X, int B, int D, float eps, float* __restrict__ Y,
+                                                       float* __restrict__ inv) {
+  const int lane = threadIdx.x & 63;
+  const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (b >= B) return;
+  const float* x = X + (int64_t)b * D;
+  const float n = sqrtf(moco_dot_wave(x, x, D, lane));
+  const float s = 1.f / fmaxf(n, eps);
+  for (int d = lane; d < D; d += 64) Y[(int64_t)b * D + d] = x[d] * s;
+  if (lane == 0) inv[b] = n > eps ? s : -s;                    // the sign marks a clamped row: there y = x / eps is linear
+}
+
+// dx = inv (dy - y <dy, y>); a clamped row: dx = dy / eps
+__global__ __launch_bounds__(256) void moco_l2norm_bwd(const float* __restrict__ dY, const float* __restrict__ Y, const float* __restrict__ inv,
+                                                       int B, int D, float* __restrict__ dX) {
+  const int lane = threadIdx.x & 63;
+  const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (b >= B) return;
+  const float* dy = dY + (int64_t)b * D;
+  const float* y = Y + (int64_t)b * D;
+  const float s = inv[b];
+  const float t = s > 0.f ? moco_dot_wave(dy, y, D, lane) : 0.f;
+  const float a = fabsf(s);
+  for (int d = lane; d < D; d += 64) dX[(int64_t)b * D + d] = a * (dy[d] - y[d] * t);
+}
+
+// ------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------
 // K-slices: about two rounds of workgroups over the device, at most `cap`; a slice is a whole number of tiles
@@ -431,29 +653,48 @@ static bool moco_vec_ok(const float* a, const float* b, int D) { return D % 4 ==
 
 #define MOCO_NK_SWITCH(D, EXPR16, EXPR8, EXPR4) ((D) > 256 ? (EXPR16) : (D) > 128 ? (EXPR8) : (EXPR4))
 
+// (spelled out: naming an instantiation to take its type would instantiate it, and BEST / COUNT exist for one value of LAB each)
+using MocoRingFn = void (*)(const float*, int, const float*, int, int, float, int, float*, f32x4*, const int64_t*, const int64_t*,
+                            const MocoCol*, MocoCol*);
+using MocoTile32Fn = void (*)(const float*, int, const float*, int, int, float, int, float*, const float*, f32x4*, const int64_t*,
+                              const int64_t*, const float*, const float*, float*, const MocoCol*, MocoCol*);
+
 // forward of either mode: the ring where the DMA can address the rows, the 32-query engine otherwise
 template <int MODE>
 static int moco_forward(const float* q, const float* memory, int B, int K, int D, float T, float* out, f32x4* part, const int64_t* klab,
-                        const int64_t* qlab, int* S_out, hipStream_t st) {
+                        const int64_t* qlab, int* S_out, hipStream_t st, const MocoCol* thr = nullptr, MocoCol* rpart = nullptr) {
   const bool lab = klab != nullptr;
   if (moco_vec_ok(q, memory, D)) {
     int per;
     const int qb = (int)slic_cdiv(B, 128);
     const int S = moco_slices(K, qb, SLIC_MOCO_PARTS, &per);
-    auto kern = lab ? MOCO_NK_SWITCH(D, (moco_ring<16, MODE, true>), (moco_ring<8, MODE, true>), (moco_ring<4, MODE, true>))
-                    : MOCO_NK_SWITCH(D, (moco_ring<16, MODE, false>), (moco_ring<8, MODE, false>), (moco_ring<4, MODE, false>));
+    auto pick = [&](auto labc) {
+      constexpr bool L = decltype(labc)::value;
+      return MOCO_NK_SWITCH(D, (moco_ring<16, MODE, L>), (moco_ring<8, MODE, L>), (moco_ring<4, MODE, L>));
+    };
+    MocoRingFn kern;
+    if constexpr (MODE == MOCO_BEST) kern = pick(std::true_type{});            // BEST runs with labels only, COUNT never reads them
+    else if constexpr (MODE == MOCO_COUNT) kern = pick(std::false_type{});
+    else kern = lab ? pick(std::true_type{}) : pick(std::false_type{});
     const size_t lds = (size_t)4 * SLIC_RT_TILE * sizeof(float);
     SLIC_LDS_LIMIT(kern, lds);
-    kern<<<dim3((unsigned)qb, (unsigned)S), dim3(256), lds, st>>>(q, B, memory, K, D, T, per, out, part, klab, qlab);
+    kern<<<dim3((unsigned)qb, (unsigned)S), dim3(256), lds, st>>>(q, B, memory, K, D, T, per, out, part, klab, qlab, thr, rpart);
     SLIC_LAUNCH_CHECK();
     *S_out = S;
   } else {
     int per;
     const int qb = (int)slic_cdiv(B, 32);
     const int S = moco_slices(K, qb, SLIC_MOCO_PARTS, &per);
-    auto kern = lab ? MOCO_NK_SWITCH(D, (moco_tile32<16, MODE, true, false>), (moco_tile32<8, MODE, true, false>), (moco_tile32<4, MODE, true, false>))
-                    : MOCO_NK_SWITCH(D, (moco_tile32<16, MODE, false, false>), (moco_tile32<8, MODE, false, false>), (moco_tile32<4, MODE, false, false>));
-    kern<<<dim3((unsigned)qb, (unsigned)S), dim3(256), 0, st>>>(q, B, memory, K, D, T, per, out, nullptr, part, klab, qlab, nullptr, nullptr, nullptr);
+    auto pick = [&](auto labc) {
+      constexpr bool L = decltype(labc)::value;
+      return MOCO_NK_SWITCH(D, (moco_tile32<16, MODE, L, false>), (moco_tile32<8, MODE, L, false>), (moco_tile32<4, MODE, L, false>));
+    };
+    MocoTile32Fn kern;
+    if constexpr (MODE == MOCO_BEST) kern = pick(std::true_type{});
+    else if constexpr (MODE == MOCO_COUNT) kern = pick(std::false_type{});
+    else kern = lab ? pick(std::true_type{}) : pick(std::false_type{});
+    kern<<<dim3((unsigned)qb, (unsigned)S), dim3(256), 0, st>>>(q, B, memory, K, D, T, per, out, nullptr, part, klab, qlab, nullptr, nullptr, nullptr,
+                                                               thr, rpart);
     SLIC_LAUNCH_CHECK();
     *S_out = S;
   }
@@ -474,7 +715,8 @@ static int moco_backward(const float* q, const float* k, const float* memory, in
   auto kern = MOCO_NK_SWITCH(D, MOCO_T32(16), MOCO_T32(8), MOCO_T32(4));
 #undef MOCO_T32
   kern<<<dim3((unsigned)qb, (unsigned)S), dim3(256), 0, st>>>(q, B, memory, K, D, T, per, nullptr, dout, nullptr, klab, qlab,
-                                                             stat ? stat + B : nullptr, stat ? stat + 2 * B : nullptr, dqpart);
+                                                             stat ? stat + B : nullptr, stat ? stat + 2 * B : nullptr, dqpart, nullptr,
+                                                             nullptr);
   SLIC_LAUNCH_CHECK();
   const unsigned nb = (unsigned)slic_cdiv((int64_t)B * D, 256);
   moco_dq_reduce<MODE == MOCO_CE_BWD><<<dim3(nb), dim3(256), 0, st>>>(dqpart, S, B, D, K, T, k, stat, dout, gscale, dq);
@@ -536,6 +778,72 @@ extern "C" int slic_moco_enqueue(float* memory, int64_t* queue_label, const floa
                B, K, index);
   SLIC_REQUIRE(!queue_label || k_label, "slic_moco_enqueue: queue_label without k_label");
   moco_enqueue<<<dim3((unsigned)slic_cdiv((int64_t)B * D, 256)), dim3(256), 0, S_(stream)>>>(memory, queue_label, k, k_label, B, K, D, index);
+  SLIC_LAUNCH_CHECK();
+  return SLIC_OK;
+}
+
+static bool moco_topks_ok(const int32_t* top_ks, int n_ks, int64_t kcap, MocoTopKs* ks) {
+  if (!top_ks || n_ks < 1 || n_ks > 8) return false;
+  ks->n = n_ks;
+  for (int i = 0; i < 8; ++i) ks->k[i] = 0;
+  for (int i = 0; i < n_ks; ++i) {
+    if (top_ks[i] < 1 || top_ks[i] > kcap || (i > 0 && top_ks[i] <= top_ks[i - 1])) return false;
+    ks->k[i] = top_ks[i];
+  }
+  return true;
+}
+
+extern "C" int slic_moco_topk_hits(const float* q, const float* k, const float* memory, int B, int K, int D, float T, const int64_t* k_label,
+                                   const int64_t* queue_label, const int32_t* top_ks, int n_ks, int32_t* rank, int32_t* hits,
+                                   void* workspace, void* stream) {
+  SLIC_REQUIRE(q && k && memory && hits && workspace, "slic_moco_topk_hits: null pointer");
+  SLIC_REQUIRE(MOCO_SHAPE_OK(B, K, D) && T > 0.f, "slic_moco_topk_hits: need 1 <= D <= 512, K D < 2^29, T > 0 (B=%d K=%d D=%d)", B, K, D);
+  SLIC_REQUIRE((k_label == nullptr) == (queue_label == nullptr), "slic_moco_topk_hits: k_label and queue_label come together");
+  SLIC_REQUIRE(((uintptr_t)workspace % 8) == 0, "slic_moco_topk_hits: unaligned workspace");
+  MocoTopKs ks;
+  SLIC_REQUIRE(moco_topks_ok(top_ks, n_ks, 8, &ks), "slic_moco_topk_hits: top_ks: 1 .. 8 ascending values in 1 .. 8 (n_ks=%d)", n_ks);
+  MocoCol* thr = (MocoCol*)workspace;                          // [B], then [SLIC_MOCO_PARTS][B] slice records
+  MocoCol* rpart = thr + B;
+  int S = 0;
+  if (k_label) {                                               // first sweep: the best positive of the queue
+    const int rc = moco_forward<MOCO_BEST>(q, memory, B, K, D, T, nullptr, nullptr, k_label, queue_label, &S, S_(stream), nullptr, rpart);
+    if (rc != SLIC_OK) return rc;
+  }
+  moco_rank_thr<<<dim3((unsigned)slic_cdiv(B, 4)), dim3(256), 0, S_(stream)>>>(q, k, B, D, T, rpart, S, thr);
+  SLIC_LAUNCH_CHECK();
+  const int rc = moco_forward<MOCO_COUNT>(q, memory, B, K, D, T, nullptr, nullptr, nullptr, nullptr, &S, S_(stream), thr, rpart);
+  if (rc != SLIC_OK) return rc;
+  moco_rank_finish<<<dim3(1), dim3(1024), 0, S_(stream)>>>(rpart, S, B, ks, rank, hits);
+  SLIC_LAUNCH_CHECK();
+  return SLIC_OK;
+}
+
+extern "C" int slic_mask_topk_hits(const float* logits, int ld, const uint8_t* mask, int ldm, int B, int C, const int32_t* top_ks, int n_ks,
+                                   int32_t* rank, int32_t* hits, void* stream) {
+  SLIC_REQUIRE(logits && mask && rank && hits, "slic_mask_topk_hits: null pointer");
+  SLIC_REQUIRE(B > 0 && C > 0 && ld >= C && ldm >= C, "slic_mask_topk_hits: need B, C > 0 and ld, ldm >= C (B=%d C=%d ld=%d ldm=%d)", B, C,
+               ld, ldm);
+  MocoTopKs ks;
+  SLIC_REQUIRE(moco_topks_ok(top_ks, n_ks, C, &ks), "slic_mask_topk_hits: top_ks: 1 .. 8 ascending values in 1 .. C (n_ks=%d)", n_ks);
+  mask_rank_rows<<<dim3((unsigned)slic_cdiv(B, 4)), dim3(256), 0, S_(stream)>>>(logits, ld, mask, ldm, B, C, rank);
+  SLIC_LAUNCH_CHECK();
+  mask_rank_hits<<<dim3(1), dim3(1024), 0, S_(stream)>>>(rank, B, ks, hits);
+  SLIC_LAUNCH_CHECK();
+  return SLIC_OK;
+}
+
+extern "C" int slic_l2normalize_fwd(const float* x, int B, int D, float eps, float* y, float* inv, void* stream) {
+  SLIC_REQUIRE(x && y && inv, "slic_l2normalize_fwd: null pointer");
+  SLIC_REQUIRE(B > 0 && D > 0 && eps > 0.f, "slic_l2normalize_fwd: need B, D, eps > 0 (B=%d D=%d)", B, D);
+  moco_l2norm_fwd<<<dim3((unsigned)slic_cdiv(B, 4)), dim3(256), 0, S_(stream)>>>(x, B, D, eps, y, inv);
+  SLIC_LAUNCH_CHECK();
+  return SLIC_OK;
+}
+
+extern "C" int slic_l2normalize_bwd(const float* dy, const float* y, const float* inv, int B, int D, float* dx, void* stream) {
+  SLIC_REQUIRE(dy && y && inv && dx, "slic_l2normalize_bwd: null pointer");
+  SLIC_REQUIRE(B > 0 && D > 0, "slic_l2normalize_bwd: need B, D > 0 (B=%d D=%d)", B, D);
+  moco_l2norm_bwd<<<dim3((unsigned)slic_cdiv(B, 4)), dim3(256), 0, S_(stream)>>>(dy, y, inv, B, D, dx);
   SLIC_LAUNCH_CHECK();
   return SLIC_OK;
 }

@@ -4,6 +4,8 @@ Checkpoint I/O of the reference's models/model_utils.py:161-211, the on-disk con
     save_checkpoint(state, is_best, model_name, output_path, is_master_proc=True, filename='checkpoint.pth.tar')
     load_checkpoint(model, checkpoint_path, classifier=False, is_master_proc=True) -> (start_epoch, best_prec1)
 
+    model_selector(cfg) for MODEL.ARCH 'info_nce' / 'uber_nce'  (models/model_utils.py:121-125)
+
 `state` is the dict the training loop builds (online_train.py:757-761): {'epoch', 'state_dict', 'best_prec1'}.
 A state_dict taken from a DistributedDataParallel wrapper carries a `module.` prefix on every key; loading strips
 it, so checkpoints move freely between wrapped / un-wrapped models and between the reference's modules and this
@@ -16,6 +18,19 @@ from collections import OrderedDict
 import torch
 
 _PREFIX = 'module.'
+
+
+def model_selector(cfg, *, kernels=None):
+    """the MoCo models of the reference's factory (models/model_utils.py:121-125) with its constants: dim 128, K 2048, m 0.999,
+    T 0.07.  The trunk is the 3D ResNet of cfg.RESNET.MODEL_DEPTH (the key the reference's '3dresnet' branch reads, :36-38;
+    18 when the config has none).  Other architectures are built directly (models.generate_model, models.r3d.r3d_model)."""
+    arch = cfg.MODEL.ARCH
+    if arch not in ('info_nce', 'uber_nce'):
+        raise NotImplementedError("model_selector builds MODEL.ARCH 'info_nce' / 'uber_nce'; got {!r}".format(arch))
+    from .infoNCE import InfoNCE, UberNCE
+    depth = int(getattr(getattr(cfg, "RESNET", None), "MODEL_DEPTH", 18))
+    cls = InfoNCE if arch == 'info_nce' else UberNCE
+    return cls('resnet{}'.format(depth), 128, 2048, 0.999, 0.07, kernels=kernels)
 
 
 def _checkpoint_dir(output_path, model_name):

@@ -9,6 +9,9 @@ structure, on the HIP path:
                             device, is_master_proc)      <- online_train.py:136-225
     iterative_cluster_step(args, cfg, encoder, eval_train_loader, epoch, cuda, device, is_master_proc)
                                                          <- online_train.py:605-662 (embed -> fit_cluster -> vid_clusters.txt -> barrier)
+    calc_mask_accuracy(output, target_mask, topk=(1,))   <- online_train.py:43-57
+    UberNCE_train_epoch(train_loader, model, criterion, optimizer, epoch, cfg, cuda, device, is_master_proc)
+                                                         <- online_train.py:60-133 (MODEL.ARCH info_nce / uber_nce over models.infoNCE)
 
 What stays the reference's: one forward over cat(views), slicing, `loss = criterion + lambda * margin term`,
 zero_grad / backward / step, the two scalar all-reduces, the text logs.  What changes: the encoder, the
@@ -181,6 +184,108 @@ def contrastive_train_epoch(train_loader, model, criterion_1, criterion_2, contr
         _append_log(cfg, 'train_loss_and_acc.txt', 'epoch:{} runtime:{} {:.4f}\n'.format(
             epoch, round((time.time() - start) / 3600, 2), losses.avg))
     return losses.avg
+
+
+def calc_mask_accuracy(output, target_mask, topk=(1,), *, kernels=None):
+    """for every k of topk the fraction of rows with a positive column of target_mask among their k largest logits
+    (online_train.py:43-57), as a list of 0-d tensors.  One device pass (slic_mask_topk_hits): the rank of the best positive,
+    columns ordered by descending logit and ascending column; no top-k indices and no scatter.  A row without a positive never hits."""
+    if kernels is None:
+        from .models.infoNCE import HipInfoNCEKernels
+        kernels = HipInfoNCEKernels()
+    if output.dim() != 2 or output.shape != target_mask.shape:
+        raise ValueError("calc_mask_accuracy expects output and target_mask of one shape [B, C], got {} and {}".format(
+            tuple(output.shape), tuple(target_mask.shape)))
+    ks = sorted(set(int(k) for k in topk))
+    if not ks or ks[0] < 1 or ks[-1] > output.shape[1] or len(ks) > 8:
+        raise ValueError("calc_mask_accuracy: at most 8 values of k in [1, {}], got {}".format(output.shape[1], tuple(topk)))
+    kernels.check(output, target_mask)
+    with torch.no_grad():
+        out = kernels.resident(output.detach())
+        mask = (target_mask.detach() != 0).to(torch.uint8).contiguous()
+        _, hits = kernels.mask_hits(out, mask, tuple(ks))
+        acc = hits.to(torch.float32) / output.shape[0]
+    return [acc[ks.index(int(k))] for k in topk]
+
+
+def UberNCE_train_epoch(train_loader, model, criterion, optimizer, epoch, cfg, cuda, device, is_master_proc=True, *, fused=True):
+    """the MoCo epoch.  fused=True takes model(..., fused=True), which is model.contrast (loss and accuracies without the
+    [B, 1 + K] logits) called through the model's forward, so that a DistributedDataParallel wrapper reduces the gradients; fused=False takes
+    model(...) and criterion / the mask loss and calc_topk_accuracy / calc_mask_accuracy on the logits, as the reference writes it.
+    The reference's `.item()` per step is kept to one read-back per LOG_INTERVAL."""
+    import numpy as np
+    from .loss.classification import calc_topk_accuracy
+    losses = AverageMeter()
+    top1_meter = AverageMeter()
+    top5_meter = AverageMeter()
+    world_size = du_helper.get_world_size()
+    model.train()
+    arch = cfg.MODEL.ARCH
+    if arch not in ('info_nce', 'uber_nce'):
+        raise ValueError("UberNCE_train_epoch: cfg.MODEL.ARCH must be 'info_nce' or 'uber_nce', got {!r}".format(arch))
+    net = model.module if hasattr(model, "module") else model
+
+    def tr(x):
+        # [B, 2 * 3, T, S, S] -> [B, 2, 3, T, S, S]; the reference takes cfg.LOSS.FEAT_DIM as the spatial size (online_train.py:75)
+        B = x.shape[0]
+        x = torch.as_tensor(x)
+        return x.view(B, 3, 2, cfg.DATA.SAMPLE_DURATION, cfg.LOSS.FEAT_DIM, cfg.LOSS.FEAT_DIM).transpose(1, 2).contiguous()
+
+    start = time.time()
+    pending = []
+    for batch_idx, (inputs, labels, index) in enumerate(train_loader):
+        inputs = np.concatenate([np.asarray(v) for v in inputs], axis=1)
+        input_seq = tr(inputs)
+        batch_size = torch.tensor(input_seq.size(0)).to(device)
+        label = labels[0]
+        if cuda:
+            input_seq = input_seq.to(device, non_blocking=True)
+            label = label.to(device, non_blocking=True)
+        if arch == 'info_nce':
+            if fused:
+                loss, (top1, top5) = model(input_seq, fused=True, topk=(1, 5))
+            else:
+                output, target = model(input_seq)
+                loss = criterion(output, target)
+                top1, top5 = calc_topk_accuracy(output, target, (1, 5))
+        else:
+            if fused:
+                loss, (top1, top5) = model(input_seq, label, fused=True, topk=(1, 5))
+            else:
+                # optimize all positive pairs, compute the mean for num_pos and for batch_size
+                output, target = model(input_seq, label)
+                loss = - (torch.nn.functional.log_softmax(output, dim=1) * target).sum(1) / target.sum(1)
+                loss = loss.mean()
+                top1, top5 = calc_mask_accuracy(output, target, (1, 5), kernels=getattr(net, "_kernels", None))
+        optimizer.zero_grad()
+        loss.backward()
+        optimizer.step()
+        loss = loss.detach()
+        if cfg.NUM_GPUS > 1:
+            [loss] = du_helper.all_reduce([loss], avg=True)
+            [batch_size_world] = du_helper.all_reduce([batch_size], avg=False)
+        else:
+            batch_size_world = batch_size
+        pending.append((loss, batch_size_world, top1, top5, batch_size))
+        log_now = ((batch_idx + 1) * world_size) % cfg.TRAIN.LOG_INTERVAL == 0
+        if log_now or batch_idx + 1 == len(train_loader):
+            for l, bsw, t1, t5, bs in pending:                              # one host sync per log interval
+                losses.update(l.item(), bsw.item())
+                top1_meter.update(float(t1), bs.item())
+                top5_meter.update(float(t5), bs.item())
+            pending = []
+            if is_master_proc and log_now:
+                print('Train Epoch: {} [{}/{} | {:.1f}%]\t'
+                      'Loss: {:.4f} ({:.4f})  Top1:{} Top5:{}'.format(epoch, losses.count, len(train_loader.dataset),
+                                                                     100. * (losses.count / len(train_loader.dataset)),
+                                                                     losses.val, losses.avg, top1_meter.val, top5_meter.val))
+    if is_master_proc:
+        print('\nTrain set: Average loss: {:.4f}\n'.format(losses.avg))
+        print('epoch:{} runtime:{}'.format(epoch, (time.time() - start) / 3600))
+        _append_log(cfg, 'train_loss_and_acc.txt', 'epoch:{} runtime:{} {:.4f}\n'.format(
+            epoch, round((time.time() - start) / 3600, 2), losses.avg))
+        print('saved to file:{}'.format('{}/tnet_checkpoints/train_loss_and_acc.txt'.format(getattr(cfg, "OUTPUT_PATH", None))))
+    return top1_meter.avg, top5_meter.avg
 
 
 def _append_log(cfg, name, line):
