@@ -328,12 +328,14 @@ def case_kmeans(rank, world, out):
         res[f"{name}/nreloc"] = km.n_relocations_
         res[f"{name}/trace_local"] = km.trace_
     # k-means++ (sklearn _kmeans.py:174-277) in a sharded run: all ranks must pick the same rows of the GLOBAL matrix
-    g = dict(np.load(os.path.join(HERE, "golden", "kmeans_d128.npz")))
-    X = g["X"]
-    N = len(X)
-    per = (N + world - 1) // world
-    shard = torch.from_numpy(X[rank * per:(rank + 1) * per]).cuda()
-    km = KMeans(n_clusters=12, n_init=2, random_state=5 + rank * 0, process_group=dist.group.WORLD).fit(shard)
+    # (the fit lives beside the recorder of its entry-point sequence: golden/make_goldens_kmeans_calls.py)
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("make_goldens_kmeans_calls", os.path.join(HERE, "golden", "make_goldens_kmeans_calls.py"))
+    mg = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mg)
+    with mg.recording() as seq:
+        km = mg.sharded_kpp_fit(KMeans, rank, world)
+    res["kpp/entry_sequence"] = np.array(seq)
     res["kpp/init_indices"] = np.asarray(km.init_indices_)
     res["kpp/labels_local"] = km.labels_
     res["kpp/centers"] = km.cluster_centers_

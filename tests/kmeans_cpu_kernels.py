@@ -13,6 +13,9 @@ def _np(t):
 
 class OracleKernels:
     device_type = "cpu"
+    uses_perm = False            # no k-permuted twins: the driver hands None for them
+    has_bf16 = False
+    kpp_run_batch = None
 
     def check(self):
         pass
@@ -63,6 +66,14 @@ class OracleKernels:
         sums.copy_(torch.from_numpy(s))
         counts.copy_(torch.from_numpy(c))
 
+    def lloyd_step(self, X, Xp, C_old, Cp_old, cnorm_old, labels, labels_old, n_changed, sums, counts, C_new, Cp_new,
+                   cnorm_new, shift, status, spherical=False):
+        """slic_kmeans_lloyd_step: one whole unsharded iteration, composed of the three steps it fuses"""
+        n_changed.zero_()
+        self.assign(X, C_old, cnorm_old, labels, labels_old, n_changed)
+        self.accumulate(X, labels, C_old.shape[0], sums, counts)
+        self.finalize(C_old, sums, counts, C_new, shift, n_changed, status, cnorm_new, spherical=spherical)
+
     def lloyd_local(self, X, Xp, C_old, Cp_old, cnorm_old, labels, labels_old, payload):
         """slic_kmeans_lloyd_local: E-step + ordered M-step -> [K*D sums | K counts | n_changed & 0xFFFFF | n_changed >> 20]"""
         K, Dp = C_old.shape
@@ -100,7 +111,7 @@ class OracleKernels:
         x = _np(X).astype(np.float64)
         out.copy_(torch.from_numpy((x / np.sqrt((x * x).sum(1, keepdims=True))).astype(np.float32)))
 
-    def finalize(self, C_old, sums, counts, C_new, shift, n_changed, status, cnorm_new=None, spherical=False):
+    def finalize(self, C_old, sums, counts, C_new, shift, n_changed, status, cnorm_new=None, C_new_perm=None, spherical=False):
         K, Dp = C_old.shape
         new, sh, tot = ok.finalize(_np(C_old), _np(sums).reshape(K, Dp), _np(counts))
         if spherical:
@@ -164,6 +175,25 @@ class OracleKernels:
             else:
                 newdist[t].copy_(torch.from_numpy(d))
             pot[t] = float(d.astype(np.float64).sum())
+
+    def kpp_run(self, X, first, K, T, uniforms, idx_out, Xp=None, xnorm=None):
+        """slic_kmeanspp_run: the K - 1 steps of _kmeans_plusplus from pre-drawn uniforms [K - 1, T], one row per step"""
+        N = X.shape[0]
+        closest = torch.empty(N, dtype=torch.float32)
+        newdist = torch.empty(T, N, dtype=torch.float32)
+        pot = torch.empty(T, dtype=torch.float64)
+        cand = torch.zeros(T, dtype=torch.int32)
+        cand[0] = first
+        idx_out[0] = first
+        self.kpp_step(X, cand, 1, None, closest, pot)
+        cur_pot = float(pot[0])
+        for c in range(1, K):
+            self.cumsum_search(closest, uniforms[c - 1] * cur_pot, T, cand)
+            self.kpp_step(X, cand, T, closest, newdist, pot)
+            b = int(np.argmin(_np(pot)))
+            cur_pot = float(pot[b])
+            closest.copy_(newdist[b])
+            idx_out[c] = cand[b]
 
     def cumsum_search(self, v, vals, T, idx_out):
         cs = np.cumsum(_np(v).astype(np.float64))

@@ -172,6 +172,20 @@ def test_sharded_hip_kmeans_equals_oracle(gpu, golden_dir, tmp_path, world):
     labels = np.concatenate([r["kpp/labels_local"] for r in res])
     assert np.array_equal(labels, ref["labels"]) and int(r0["kpp/n_iter"]) == ref["n_iter"]
     assert float(r0["kpp/inertia"]) == pytest.approx(ref["inertia"], rel=1e-9)
+    # the entry points of that fit, in order, against the driver that gathered and imaged the matrix again for every run of the n_init
+    # loop (golden/make_goldens_kmeans_calls.py; recorded where it could be: one rank): the same calls but for fewer of the three imaging ones
+    key = "sharded_kpp_w1" + ("_bf16" if os.environ.get("SLIC_KMEANS_BF16", "0") == "1" else "")
+    if world == 1:
+        import json
+        with open(os.path.join(golden_dir, "kmeans_entry_sequence.json")) as f:
+            parent = json.load(f)["sequences"][key]
+        got, at = r0["kpp/entry_sequence"].tolist(), 0
+        for name in parent:
+            if at < len(got) and got[at] == name:
+                at += 1
+            else:
+                assert name in ("slic_kmeans_permute_k8", "slic_kmeans_cnorm", "slic_kmeans_bf16_image"), (name, at)
+        assert at == len(got) < len(parent), got[at:]
 
 
 @pytest.mark.parametrize("world", _worlds())

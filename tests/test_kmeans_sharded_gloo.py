@@ -35,14 +35,28 @@ def _worker(rank, world, port, case, out_dir, exchange):
         per = (N + world - 1) // world
         shard = torch.from_numpy(X[rank * per:(rank + 1) * per])
         calls = {"n": 0}
+        log = []                                                   # the two halves of every iteration and the collectives, in call order
         for fn in ("all_reduce", "all_gather_into_tensor", "all_gather", "broadcast"):
             def counted(*a, _f=getattr(torch.distributed, fn), **kw):
                 calls["n"] += 1
+                log.append("collective")
                 return _f(*a, **kw)
             setattr(torch.distributed, fn, counted)
+
+        class Logged(OracleKernels):
+            def lloyd_local(self, *a, **kw):
+                log.append("lloyd_local")
+                return super().lloyd_local(*a, **kw)
+
+            def lloyd_global(self, *a, **kw):
+                log.append("lloyd_global")
+                return super().lloyd_global(*a, **kw)
+
         km = KMeans(n_clusters=init.shape[0], init=init, n_init=1, process_group=torch.distributed.group.WORLD,
-                    kernels=OracleKernels(), trace=True, exchange=exchange).fit(shard)
+                    kernels=Logged(), trace=True, exchange=exchange).fit(shard)
         n_coll = calls["n"]
+        with open(os.path.join(out_dir, f"log_r{rank}.txt"), "w") as f:
+            f.write("\n".join(log))
         # reference-shaped helpers (misc/distributed_helper.py:41-64)
         t = torch.tensor([float(rank + 1)])
         du.all_reduce([t], avg=True)
@@ -88,6 +102,12 @@ def test_sharded_kmeans_two_ranks_gloo(golden_dir, tmp_path, name, exchange, mon
         # ONE collective per Lloyd iteration: n_iter + 1 launches (the loop runs one iteration ahead of
         # the host) + the fit's fixed set-up / wrap-up exchanges (shard sizes, column means, tolerance, inertia)
         assert int(r0["n_coll"]) <= int(r0["n_iter"]) + 1 + 6, (int(r0["n_coll"]), int(r0["n_iter"]))
+        # the order inside an iteration, on every rank: local half -> the ONE collective -> global half, n_iter + 1 times.  The log is
+        # cut at the first local half (before it: the set-up exchanges) and behind the last global half (after it: the inertia's)
+        for r in range(world):
+            log = open(os.path.join(tmp_path, f"log_r{r}.txt")).read().split("\n")
+            loop = log[log.index("lloyd_local"):len(log) - log[::-1].index("lloyd_global")]
+            assert loop == ["lloyd_local", "collective", "lloyd_global"] * (int(r0["n_iter"]) + 1), loop
 
 
 def _failing_worker(rank, world, port, case, out_dir):
@@ -104,14 +124,27 @@ def _failing_worker(rank, world, port, case, out_dir):
         per = (len(X) + world - 1) // world
         shard = torch.from_numpy(X[rank * per:(rank + 1) * per])
 
+        log = []                                                    # the halves of every iteration and the collectives, in call order
+        for fn in ("all_reduce", "all_gather_into_tensor", "all_gather", "broadcast"):
+            def counted(*a, _f=getattr(torch.distributed, fn), **kw):
+                log.append("collective")
+                return _f(*a, **kw)
+            setattr(torch.distributed, fn, counted)
+
         class Failing(OracleKernels):
             n = 0
 
             def lloyd_local(self, *a, **kw):
                 Failing.n += 1
                 if rank == 1 and Failing.n == 3:                    # the third iteration's local half of rank 1
+                    log.append("lloyd_local FAILED")
                     raise MemoryError("injected: the local half of iteration 2 failed on rank 1")
+                log.append("lloyd_local")
                 return super().lloyd_local(*a, **kw)
+
+            def lloyd_global(self, *a, **kw):
+                log.append("lloyd_global")
+                return super().lloyd_global(*a, **kw)
 
         t0 = time.time()
         msg = "no exception"
@@ -124,6 +157,8 @@ def _failing_worker(rank, world, port, case, out_dir):
         torch.distributed.barrier()      # both ranks get here (each caught its exception): do not tear a socket down under the peer's last receive
         with open(os.path.join(out_dir, f"fail_r{rank}.txt"), "w") as f:
             f.write(f"{dt:.3f}\n{msg}\n")
+        with open(os.path.join(out_dir, f"fail_log_r{rank}.txt"), "w") as f:
+            f.write("\n".join(log))
     finally:
         torch.distributed.destroy_process_group()
 
@@ -138,6 +173,12 @@ def test_sharded_kmeans_local_failure_reaches_every_rank(golden_dir, tmp_path):
     assert r1[1].startswith("MemoryError: injected"), r1
     assert r0[1].startswith("SlicError") and "peer" in r0[1], r0
     assert float(r0[0]) < 60 and float(r1[0]) < 60
+    # the poison rule's order on the failing rank: two whole iterations, then the failed local half is followed by that iteration's
+    # collective all the same, and no global half is launched for it or after it
+    log = open(os.path.join(tmp_path, "fail_log_r1.txt")).read().split("\n")
+    at = log.index("lloyd_local FAILED")
+    assert log[log.index("lloyd_local"):at] == ["lloyd_local", "collective", "lloyd_global"] * 2, log
+    assert log[at + 1] == "collective" and "lloyd_global" not in log[at:] and "lloyd_local" not in log[at + 1:], log
 
 
 def test_single_process_driver_matches_oracle_cpu(golden_dir):

@@ -11,6 +11,12 @@ Only control flow lives here; every reduction/contraction is a HIP kernel reache
 `HipKernels` (one method per C-ABI entry point).  One host sync per Lloyd iteration (a 4-double
 status word).
 
+A Lloyd iteration has exactly two forms, and a run picks its form — and its E-step precision — once, before the loop:
+    unsharded : ONE fused foreign call (slic_kmeans_lloyd_step[_bf16]: E-step, ordered M-step, averaging, status word);
+    sharded   : local half -> poison rule -> ONE collective -> global half (below).
+What a sharded fit asks of its process group (route of the collective, payload dtype, bounded waits, the small set-up exchanges)
+is resolved once per fit: clustering/kmeans_exchange.py.
+
 Multi-GPU: pass `process_group`; X is then this rank's contiguous row shard
 (rank order == row order).  An iteration is two foreign calls around ONE collective over RCCL/xGMI
 (it replaces the rank-0 k-means + barrier of online_train.py:625-662):
@@ -24,9 +30,11 @@ Multi-GPU: pass `process_group`; X is then this rank's contiguo
 
 precision="bf16" (DESIGN.md §7f): the E-step of every iteration, sharded or not, and the final relabelling run as a certified bf16
 candidate pass with exact rescoring (slic_kmeans_lloyd_step_bf16 / _lloyd_local_bf16 / _assign_bf16) — the same labels to the bit.  The
-bf16 image and the norms of the centred rows are made once per fit; its three counters are read once, after the fit (bf16_stats_).
+bf16 image and the norms of the centred rows are made once per fit, like the k-permuted copy and what k-means++ reads, and handed
+down to the runs; its three counters are read once, after the fit (bf16_stats_).
 """
 import ctypes
+import functools
 import os
 import time
 
@@ -35,6 +43,7 @@ import torch
 
 from .. import _lib
 from .._lib import call, ptr, stream
+from .kmeans_exchange import Exchange, _slic_oneshot  # noqa: F401 — tests/dist_gpu_worker.py reaches the one-shot set-up through this module
 
 
 _POISON = float(2 ** 40)      # in the n_changed high slot of a sharded payload: this rank's local half failed (exact in fp32 and fp64, sums of <= 16 too)
@@ -42,9 +51,20 @@ _POISON = float(2 ** 40)      # in the n_changed high slot of a sharded payload:
 class HipKernels:
     """Thin argument marshalling for the k-means entry points of libslic_hip.so.  The only kernel
     provider the package ships; `KMeans(kernels=...)` exists so the multi-process control flow can be
-    exercised under gloo on a GPU-less host by the tests (tests/kmeans_cpu_kernels.py)."""
+    exercised under gloo on a GPU-less host by the tests (tests/kmeans_cpu_kernels.py).
+
+    What `KMeans` calls on its provider — a second provider implements these with the same argument meaning:
+        check  to_device  col_stats  sub_rowvec  l2norm_rows  cnorm  dist_to_assigned  sum_f64            (fit, inertia)
+        lloyd_step | lloyd_local + lloyd_global   finalize  assign   select_far  apply_relocation           (a Lloyd run)
+        kpp_run                                                                                             (k-means++)
+    and what a provider may lack, declared as class attributes instead of being probed for:
+        uses_perm      True: the E-step reads k-permuted twins of the rows and the centres (permute_k8, assign_perm)
+        has_bf16       True: bf16_image, assign_bf16, lloyd_step_bf16, lloyd_local_bf16 exist (they need uses_perm)
+        kpp_run_batch  the lock-step seeding of an n_init loop (it needs uses_perm), or None"""
 
     device_type = "cuda"
+    uses_perm = True       # E-step on k-permuted copies of X and the centres (LDS-DMA kernel)
+    has_bf16 = True
 
     def check(self):
         if not torch.cuda.is_available():
@@ -75,8 +95,6 @@ class HipKernels:
         ws = _lib.workspace(_lib.load().slic_kmeans_assign_workspace_bytes(N, K), X.device, "km_assign")
         call("slic_kmeans_assign", ptr(X), N, Dp, X.stride(0), ptr(C), K, C.stride(0), ptr(cnorm), ptr(labels),
              ptr(labels_old), ptr(n_changed), None, ptr(ws), stream())
-
-    uses_perm = True       # E-step on k-permuted copies of X and the centres (LDS-DMA kernel)
 
     def permute_k8(self, X, Xp):
         call("slic_kmeans_permute_k8", ptr(X), X.shape[0], X.shape[1], X.stride(0), ptr(Xp), Xp.stride(0), stream())
@@ -166,7 +184,6 @@ class HipKernels:
 
     def kpp_run_batch(self, Xp, xnorm, firsts, K, T, uniforms, idx_out):
         """all R = len(firsts) initialisations of an n_init loop in lock-step (slic_kmeanspp_run_batch)"""
-        import ctypes
         N, Dp = Xp.shape
         R = len(firsts)
         arr = (ctypes.c_int32 * R)(*[int(f) for f in firsts])
@@ -217,141 +234,19 @@ class HipKernels:
         call("slic_cumsum_search", ptr(v), v.numel(), ptr(vals), T, ptr(idx_out), ptr(ws), stream())
 
 
-# process group -> slic_comm* (an RCCL communicator of the library's own, created once per group).  Keyed on the group OBJECT through
-# weak references: a destroyed group's id() may be re-used by a new group with other members, and a stale communicator would hang or
-# reduce over the wrong ranks; when the group goes away its communicator is destroyed with it.
-import weakref
-
-_COMMS = weakref.WeakKeyDictionary()
-
-
-_EXITING = []
-
-
-def _mark_exiting():
-    _EXITING.append(True)
-
-
-class _CommHandle:
-    """owns one slic_comm*: slic_comm_destroy (finalize, bounded settle, destroy) when the handle dies because its group was collected;
-    slic_comm_abort at interpreter exit — torch may have torn its process group down by then and a peer may be gone: the exit path
-    must not wait for anybody"""
-
-    _hooked = False
-
-    def __init__(self, ptr_):
-        self.ptr = ptr_
-        self._fin = weakref.finalize(self, _CommHandle._close, ptr_)
-        if not _CommHandle._hooked:
-            # registered AFTER weakref's own exit hook (created with the first finalize object), so it runs BEFORE it (LIFO)
-            import atexit
-            atexit.register(_mark_exiting)
-            _CommHandle._hooked = True
-
-    @staticmethod
-    def _close(ptr_):
-        try:
-            lib = _lib.load()
-            (lib.slic_comm_abort if _EXITING else lib.slic_comm_destroy)(ptr_)
-        except Exception:
-            pass
-
-
-def comm_timeout_ms():
-    """deadline of the library communicator's waits (SLIC_COMM_TIMEOUT_MS, default five minutes — torch.distributed's own collectives
-    default to ten): a peer that never joins makes every rank raise instead of hang"""
-    return int(os.environ.get("SLIC_COMM_TIMEOUT_MS", "300000"))
-
-
-def _slic_comm(pg, dev):
-    """the C-ABI communicator for the sharded iteration's all-reduce (include/slic_hip.h: slic_comm_create_timeout): rank 0 of the
-    group draws the unique id, torch.distributed carries it to the others, every rank joins on its device — under a deadline"""
-    import ctypes
-    h = _COMMS.get(pg)
-    if h is not None:
-        return h.ptr
-    lib = _lib.load()
-    W, rank = torch.distributed.get_world_size(pg), torch.distributed.get_rank(pg)
-    idt = torch.zeros(128, dtype=torch.uint8, device=dev)
-    if rank == 0:
-        buf = (ctypes.c_ubyte * 128)()
-        _lib.check(lib.slic_comm_unique_id(buf), "slic_comm_unique_id")
-        idt.copy_(torch.tensor(list(buf), dtype=torch.uint8))
-    torch.distributed.broadcast(idt, src=torch.distributed.get_global_rank(pg, 0), group=pg)
-    raw = bytes(idt.cpu().numpy().tobytes())
-    comm = ctypes.c_void_p()
-    _lib.check(lib.slic_comm_create_timeout(raw, W, rank, comm_timeout_ms(), ctypes.byref(comm)), "slic_comm_create_timeout")
-    _COMMS[pg] = _CommHandle(comm)
-    return comm
-
-
-_ONESHOTS = weakref.WeakKeyDictionary()
-
-
-class _OneshotHandle:
-    """owns one slic_oneshot*; destroyed with its process group or at interpreter exit (slic_oneshot_destroy never waits for a peer)"""
-
-    def __init__(self, ptr_, max_n):
-        self.ptr, self.max_n = ptr_, max_n
-        self._fin = weakref.finalize(self, _OneshotHandle._close, ptr_)
-
-    @staticmethod
-    def _close(ptr_):
-        try:
-            _lib.load().slic_oneshot_destroy(ptr_)
-        except Exception:
-            pass
-
-
-def _pg_all_gather_bytes(pg, raw, dev):
-    """all-gather one small byte string per rank over the process group (RCCL: device tensors; gloo: host tensors) -> bytes, rank order"""
-    W = torch.distributed.get_world_size(pg)
-    on_dev = torch.distributed.get_backend(pg) == "nccl"
-    t = torch.frombuffer(bytearray(raw), dtype=torch.uint8).clone()
-    t = t.to(dev) if on_dev else t
-    out = torch.empty(W * t.numel(), dtype=torch.uint8, device=t.device)
-    torch.distributed.all_gather_into_tensor(out, t, group=pg)
-    return bytes(out.cpu().numpy().tobytes())
-
-
-def _slic_oneshot(pg, dev, n):
-    """the one-shot exchange of the sharded iteration (include/slic_hip.h: slic_oneshot_*): every rank allocates its inbox, the IPC handles
-    travel over the process group, every rank maps its peers.  One communicator per group, re-made when a larger payload comes along."""
-    h = _ONESHOTS.get(pg)
-    if h is not None and h.max_n >= n:
-        return h.ptr
-    lib = _lib.load()
-    W, rank = torch.distributed.get_world_size(pg), torch.distributed.get_rank(pg)
-    if W > 1 and os.environ.get("SLIC_ONESHOT_MULTI_GPU", "0") != "1":
-        # EXPERIMENTAL between GPUs: every test of this exchange ran its ranks as processes on ONE device (one-GPU boxes); a run over xGMI has
-        # never been compared with the all-reduce route.  Ranks on different devices must opt in (ADVICE round 5).  Every rank sees the same
-        # gathered identities, so every rank raises (or none does).
-        import socket
-        pr = torch.cuda.get_device_properties(dev)
-        ident = "%s/%s/%s/%s/%s" % (socket.gethostname(), getattr(pr, "uuid", ""), getattr(pr, "pci_domain_id", ""), getattr(pr, "pci_bus_id", ""),
-                                    getattr(pr, "pci_device_id", ""))
-        ids = _pg_all_gather_bytes(pg, ident.encode()[:96].ljust(96, b"\0"), dev)
-        if len({ids[i * 96:(i + 1) * 96] for i in range(W)}) > 1:
-            raise _lib.SlicError("exchange='oneshot' between different GPUs is experimental (never verified against the RCCL all-reduce on a multi-GPU "
-                                 "node): set SLIC_ONESHOT_MULTI_GPU=1 to opt in, or use exchange='allreduce'")
-    hb = 64
-    mine = (ctypes.c_ubyte * hb)()
-    comm = ctypes.c_void_p()
-    with torch.cuda.device(dev):
-        _lib.check(lib.slic_oneshot_create(W, rank, n, comm_timeout_ms(), ctypes.byref(comm), mine), "slic_oneshot_create")
-        allh = _pg_all_gather_bytes(pg, bytes(mine), dev)
-        _lib.check(lib.slic_oneshot_connect(comm, allh), "slic_oneshot_connect")
-    # nobody may push into an inbox before its owner has mapped... (a push only needs the PUSHER's mapping; the barrier keeps a fast rank's
-    # first exchange from racing a slow rank's connect bookkeeping and gives create / connect failures a common point to surface)
-    torch.distributed.barrier(group=pg)
-    _ONESHOTS[pg] = _OneshotHandle(comm, n)
-    return comm
-
-
 def _dist_on(pg):
     # a process group of ONE rank still takes the sharded path (all-gather of one partial, ordered add): that is
     # how a single-GPU box exercises the RCCL code path
     return pg is not None and torch.distributed.is_initialized()
+
+
+def _kpp_trials(K):
+    """n_local_trials of _kmeans_plusplus: 2 + int(ln K)"""
+    T = 2 + int(np.log(K))
+    if T > 16:
+        raise ValueError(f"k-means++ with n_clusters={K}: {T} local trials per centre, slic_kmeanspp_run takes at most 16 "
+                         "(n_clusters < 3 269 018); pass init= explicitly")
+    return T
 
 
 class KMeans:
@@ -384,6 +279,9 @@ class KMeans:
             raise ValueError(f"precision={precision!r}: 'fp32' or 'bf16'")
         self.precision = precision
         self.bf16_stats_ = None
+        self._ex = None                        # the current fit's Exchange (kmeans_exchange.py); None: not sharded
+        self._fit_rs = None
+        self._side = None
 
     # ------------------------------------------------------------------ helpers
     def _rng(self):
@@ -392,48 +290,31 @@ class KMeans:
         if rs is None:
             return np.random.mtrand._rand     # sklearn check_random_state(None): numpy's global RandomState
         if isinstance(rs, (int, np.integer)):
-            if getattr(self, "_fit_rs", None) is None:
+            if self._fit_rs is None:
                 self._fit_rs = np.random.RandomState(rs)
             return self._fit_rs
         return rs
 
-    def _host_staged(self, t):
-        """device tensors over a gloo group (two ranks sharing ONE GPU — how a one-GPU box runs exchange='oneshot' with two processes; RCCL
-        cannot put two ranks on a device) go through host copies; RCCL groups and host tensors are used as they are"""
-        return t.is_cuda and torch.distributed.get_backend(self.process_group) == "gloo"
-
-    def _gather(self, t):
-        """all-gather a per-rank tensor [*] -> [W, *] (same shape on every rank)"""
-        W = torch.distributed.get_world_size(self.process_group)
-        src = t.contiguous().reshape(-1)
-        if self._host_staged(t):
-            src = src.cpu()
-        flat = torch.empty(W * t.numel(), dtype=t.dtype, device=src.device)    # concatenated form (gloo and RCCL)
-        torch.distributed.all_gather_into_tensor(flat, src, group=self.process_group)
-        return flat.to(t.device).view((W,) + tuple(t.shape))
-
-    def _col_stats(self, X):
-        """global column sum / sum of squares as float64 numpy (rank partials added in rank order)"""
-        cs = self.k.col_stats(X)
-        if self._sharded:
-            allcs = self._gather(cs).cpu().numpy()      # [W, 2, Dp]
-            tot = np.zeros_like(allcs[0])
-            for r in range(allcs.shape[0]):
-                tot += allcs[r]
-            return tot
-        return cs.cpu().numpy()
+    def _rank_sum(self, t):
+        """a float64 device tensor -> numpy; in a sharded fit the ranks' tensors added in rank order"""
+        if self._ex is None:
+            return t.cpu().numpy()
+        parts = self._ex.gather(t).cpu().numpy()           # [W, *]
+        tot = np.zeros_like(parts[0])
+        for r in range(parts.shape[0]):
+            tot += parts[r]
+        return tot
 
     # ------------------------------------------------------------------ fit
     def fit(self, X):
         self._fit_rs = None
         self.init_indices_log_ = []
-        self._bf16 = self._use_bf16(int(np.shape(X)[1]))             # raises for precision='bf16' outside its domain: before any launch
+        bf16 = self._use_bf16(int(np.shape(X)[1]))                   # raises for precision='bf16' outside its domain: before any launch
         self.bf16_stats_ = None
         self.k.check()
         X = self.k.to_device(X)
         N, D = X.shape
         K = self.n_clusters
-        self._sharded = _dist_on(self.process_group)
         dev = X.device
         # pad the feature dim to a multiple of 8 with zero columns (they add exact zeros to every chain)
         Dp = (D + 7) // 8 * 8
@@ -441,14 +322,14 @@ class KMeans:
             Xp = torch.zeros(N, Dp, dtype=torch.float32, device=dev)
             Xp[:, :D] = X
             X = Xp
-        if self._sharded:
-            sizes = self._gather(torch.tensor([N], dtype=torch.int64, device=dev)).cpu().numpy().reshape(-1)
-            rank = torch.distributed.get_rank(self.process_group)
-            self._row0 = int(sizes[:rank].sum())
-            self._sizes = sizes
+        if _dist_on(self.process_group):
+            self._ex = ex = Exchange(self.process_group, self.exchange, dev, K * Dp + K + 2)     # [sums | counts | n_changed lo, hi]
+            self.communicator_kind_, self.payload_bytes_ = ex.communicator_kind_, ex.payload_bytes_
+            sizes = ex.gather(torch.tensor([N], dtype=torch.int64, device=dev)).cpu().numpy().reshape(-1)
+            self._row0 = int(sizes[:ex.rank].sum())
             Ng = int(sizes.sum())
         else:
-            self._row0, self._sizes, Ng = 0, np.array([N]), N
+            self._ex, self._row0, sizes, Ng = None, 0, np.array([N]), N
 
         if self.spherical:
             # SphericalKMeans.fit: X = normalize(X); the data is NOT centred and tol is used as given
@@ -458,21 +339,18 @@ class KMeans:
             tol_abs = self.tol
         else:
             # X -= X.mean(axis=0)   (_kmeans.py:1479-1481)
-            cs = self._col_stats(X)
+            cs = self._rank_sum(self.k.col_stats(X))                    # global column sums / sums of squares
             mean = (cs[0] / float(Ng)).astype(np.float32)
             mean_d = torch.from_numpy(mean).to(dev)
             Xc = torch.empty_like(X)
             self.k.sub_rowvec(X, mean_d, Xc)
-        # tol = mean(var(Xc, axis=0)) * tol   (_tolerance, _kmeans.py:279-288)
-        if self.spherical:
-            pass
-        elif self.tol == 0:
+            # tol = mean(var(Xc, axis=0)) * tol   (_tolerance, _kmeans.py:279-288)
             tol_abs = 0.0
-        else:
-            cs2 = self._col_stats(Xc)
-            m = cs2[0] / float(Ng)
-            var = cs2[1] / float(Ng) - m * m
-            tol_abs = float(var[:D].sum() / D) * self.tol
+            if self.tol != 0:
+                cs2 = self._rank_sum(self.k.col_stats(Xc))
+                m = cs2[0] / float(Ng)
+                var = cs2[1] / float(Ng) - m * m
+                tol_abs = float(var[:D].sum() / D) * self.tol
         self.tol_abs_ = tol_abs
 
         inits = self.init
@@ -486,19 +364,19 @@ class KMeans:
             inits = [np.asarray(a, np.float32)]
         n_runs = self.n_init if inits is None else len(inits)
 
-        self._bf16_stats = torch.zeros(3, dtype=torch.int32, device=dev) if self._bf16 else None
-        best = None
-        seeded = self._kmeans_plusplus_all(Xc, K, n_runs) if (inits is None and n_runs > 1) else None
+        best = est = None
+        seed = self._seed_rows(Xc, sizes, K) if inits is None else None
+        seeds = self._kmeans_plusplus(seed, K, n_runs) if inits is None else None
         for run in range(n_runs):
-            if seeded is not None:
-                C0 = seeded[run]
-            elif inits is None:
-                C0 = self._kmeans_plusplus(Xc, K)          # rows of the centred matrix
+            if inits is None:
+                C0 = next(seeds)                           # rows of the centred matrix
             else:
                 c = np.zeros((K, Dp), np.float32)
                 c[:, :D] = inits[run] - mean[None, :D]
                 C0 = torch.from_numpy(c).to(dev)
-            res = self._lloyd_single(Xc, C0, tol_abs)
+            if est is None:
+                est = self._estep_images(Xc, seed, bf16)   # behind the first seeding: where these launches have always been
+            res = self._lloyd_single(est, C0, tol_abs)
             if best is None or res["inertia"] < best["inertia"]:
                 best = res
         self.labels_ = best["labels"].cpu().numpy()                 # np.int32, like sklearn's labels_
@@ -509,15 +387,15 @@ class KMeans:
         self.strict_ = best["strict"]
         self.n_relocations_ = best["n_relocations"]
         self.trace_ = best.get("trace")
-        if self._bf16:
-            st = self._bf16_stats.cpu().tolist()                    # read once per fit
+        if bf16:
+            st = est[4].cpu().tolist()                              # read once per fit
             self.bf16_stats_ = dict(rows_rescored=st[0], rows_overflowed=st[1], candidates=st[2])
         return self
 
     def _use_bf16(self, D):
         """does this fit run the certified bf16 E-step?  An explicit precision='bf16' outside the domain is an error, never a silent fp32 run"""
         Dp = (D + 7) // 8 * 8
-        able = hasattr(self.k, "assign_bf16") and bool(getattr(self.k, "uses_perm", False))
+        able = self.k.has_bf16 and self.k.uses_perm
         if self.precision == "bf16":
             if Dp > 512:
                 raise ValueError(f"precision='bf16' takes D <= 512 (D={D}); use precision='fp32'")
@@ -526,13 +404,51 @@ class KMeans:
             return True
         return self.precision is None and os.environ.get("SLIC_KMEANS_BF16", "0") == "1" and Dp <= 512 and able
 
+    # ------------------------------------------------------------------ what a fit makes once and hands to its runs
+    def _seed_rows(self, Xc, sizes, K):
+        """what k-means++ reads -> (Xs, its k-permuted copy, its squared row norms): Xs is the centred matrix itself, or — sharded — the
+        all-gathered one every rank seeds on (the provider's own images only where it uses_perm)"""
+        _kpp_trials(K)                                                                  # raises before anything is launched
+        k, ex = self.k, self._ex
+        if ex is None:
+            Xs = Xc
+        elif int(sizes.min()) == int(sizes.max()):
+            Xs = ex.gather(Xc).reshape(-1, Xc.shape[1]).contiguous()
+        else:
+            pad = torch.zeros(int(sizes.max()), Xc.shape[1], dtype=Xc.dtype, device=Xc.device)
+            pad[: Xc.shape[0]] = Xc
+            allp = ex.gather(pad)
+            Xs = torch.cat([allp[r, : int(sizes[r])] for r in range(len(sizes))], 0).contiguous()
+        if not k.uses_perm:
+            return Xs, None, None
+        Xsp = torch.empty_like(Xs)
+        xn = torch.empty(Xs.shape[0], dtype=torch.float32, device=Xs.device)
+        k.permute_k8(Xs, Xsp)
+        k.cnorm(Xs, xn)
+        return Xs, Xsp, xn
+
+    def _estep_images(self, Xc, seed, bf16):
+        """what every E-step of the fit reads -> (Xc, k-permuted copy, bf16 image, row norms, the bf16 counters); None where not used"""
+        k = self.k
+        Xp = Xb = xnb = bstats = None
+        if k.uses_perm and seed is not None and seed[0] is Xc:
+            Xp = seed[1]                                                                # the copy k-means++ already made
+        elif k.uses_perm:
+            Xp = torch.empty_like(Xc)
+            k.permute_k8(Xc, Xp)
+        if bf16:
+            Xb, xnb = k.bf16_image(Xc, want_norms=True)
+            bstats = torch.zeros(3, dtype=torch.int32, device=Xc.device)
+        return Xc, Xp, Xb, xnb, bstats
+
     # ------------------------------------------------------------------ one Lloyd run
-    def _lloyd_single(self, Xc, C, tol_abs):
+    def _lloyd_single(self, est, C, tol_abs):
         """_kmeans_single_lloyd with the host loop running ONE iteration behind the device: iteration it+1 is enqueued
         before iteration it's 4-double status word is read, so the read-back (and this Python) hide under the next
         E-step.  A speculatively launched iteration is simply ignored when the previous one turns out to have converged
         (it only reads the state it would need to keep: rings of 3 centre / label buffers, 2 partial-sum buffers)."""
-        k = self.k
+        k, ex = self.k, self._ex
+        Xc, Xp, Xb, xnb, bstats = est
         N, Dp = Xc.shape
         K = C.shape[0]
         dev = Xc.device
@@ -540,59 +456,25 @@ class KMeans:
         Cb = [C.contiguous().clone(), torch.empty_like(C), torch.empty_like(C)]          # iteration it: Cb[it%3] -> Cb[(it+1)%3]
         Lb = [torch.full((N,), -1, dtype=torch.int32, device=dev) for _ in range(3)]      # labels of iteration it: Lb[it%3]
         cnorm = [torch.empty(K, dtype=torch.float32, device=dev) for _ in range(3)]        # norms of Cb[i]: written by finalize
-        perm = bool(getattr(k, "uses_perm", False))
+        Cp = [torch.empty_like(C) if k.uses_perm else None for _ in range(3)]              # permuted twins of Cb
         sph = dict(spherical=True) if self.spherical else {}
-        if perm:
-            Xp = self._permuted(Xc)                                                        # once per fit, shared by the inits
-            Cp = [torch.empty_like(C) for _ in range(3)]                                   # permuted twins of Cb
-        else:
-            Cp = [None] * 3
-        bf = bool(getattr(self, "_bf16", False))
-        if bf:
-            Xb, xnb = self._bf16_image(Xc)                                                 # once per fit, shared by the inits
-            Cimg = torch.empty(K, Xb.shape[1], dtype=torch.int16, device=dev)              # the centres' image: rewritten every iteration
-            bstats = self._bf16_stats
         n_changed = [torch.zeros(1, dtype=torch.int32, device=dev) for _ in range(2)]
-        part = [torch.empty(K * Dp + K, dtype=torch.float32, device=dev) for _ in range(2)]   # [sums | counts]: the all-gather unit
         shift = torch.empty(K, dtype=torch.float32, device=dev)
         status = [torch.empty(4, dtype=torch.float64, device=dev) for _ in range(2)]
         host = [torch.empty(4, dtype=torch.float64).pin_memory() if on_gpu else torch.empty(4, dtype=torch.float64) for _ in range(2)]
         ev = [torch.cuda.Event() if on_gpu else None for _ in range(2)]
         done = [torch.cuda.Event() if on_gpu else None for _ in range(2)]
         side = self._side_stream(dev) if on_gpu else None
-        comm = None
-        if self._sharded:
-            W = torch.distributed.get_world_size(self.process_group)
-            PL = K * Dp + K + 2                                          # [sums | counts | n_changed lo, hi]
-            if self.exchange in ("allreduce", "oneshot"):
-                payload = [torch.empty(1, PL, dtype=torch.float64, device=dev) for _ in range(2)]
-                parts = payload                                          # reduced in place
-            else:
-                payload = [torch.empty(1, PL, dtype=torch.float32, device=dev) for _ in range(2)]
-                parts = [torch.empty(W, PL, dtype=torch.float32, device=dev) for _ in range(2)]
-            gsums = [torch.empty(K * Dp, dtype=torch.float32, device=dev) for _ in range(2)]
-            gcounts = [torch.empty(K, dtype=torch.float32, device=dev) for _ in range(2)]
-            # the all-reduce goes through torch.distributed's process group (RCCL on the GPU, gloo in the CPU tests): its
-            # collectives carry the group's timeout and it is the path every multi-rank test runs.  SLIC_KMEANS_COMM=slic opts
-            # into the library's own RCCL communicator (slic_allreduce_f64 on the compute stream, the C ABI's collective for
-            # callers without torch.distributed); its waits are bounded too (slic_comm_create_timeout / slic_comm_wait)
-            if (self.exchange == "allreduce" and on_gpu and torch.distributed.get_backend(self.process_group) == "nccl"
-                    and os.environ.get("SLIC_KMEANS_COMM", "torch") == "slic"):
-                comm = _slic_comm(self.process_group, dev)
-            # exchange="oneshot": the library's one-shot all-to-all over peer-mapped memory (slic_allreduce_oneshot_f64: one kernel per
-            # iteration instead of a ring all-reduce; csrc/oneshot.hip).  The process group only carries the IPC handles at set-up.
-            oneshot = None
-            if self.exchange == "oneshot":
-                assert on_gpu, "exchange='oneshot' moves device memory between GPUs"
-                oneshot = _slic_oneshot(self.process_group, dev, PL)
-            # what a benchmark line reports about the iteration's one exchange (bench.py: secondary.exchange)
-            self.communicator_kind_ = ("slic_oneshot (peer-mapped inboxes, one kernel per exchange; no RCCL in the loop)" if oneshot is not None else
-                                       "slic_comm (the library's own RCCL communicator, slic_allreduce_f64)" if comm is not None else
-                                       f"torch.distributed process group ({torch.distributed.get_backend(self.process_group)})")
-            self.payload_bytes_ = int(payload[0].numel() * payload[0].element_size())
+        # the E-step's precision, bound ONCE per run.  estep(Cin, Cpin, ...) is the fused step (unsharded) or the local half (sharded) with
+        # the rows and their images in place; the bf16 forms take scratch for the centres' image where the fp32 forms take the permuted centres
+        if Xb is None:
+            estep = functools.partial(k.lloyd_step if ex is None else k.lloyd_local, Xc, Xp)
         else:
-            gsums = [p[: K * Dp] for p in part]
-            gcounts = [p[K * Dp:] for p in part]
+            step = k.lloyd_step_bf16 if ex is None else k.lloyd_local_bf16
+            Cimg = torch.empty(K, Xb.shape[1], dtype=torch.int16, device=dev)              # the centres' image: rewritten every iteration
+
+            def estep(Cin, Cpin, *a, **kw):
+                step(Xc, Xp, Xb, xnb, Cin, Cimg, *a, bstats, **kw)
 
         def read_back(sl):
             if on_gpu:
@@ -607,91 +489,57 @@ class KMeans:
                 host[sl].copy_(status[sl])
 
         local_failure = []
+        if ex is None:
+            part = [torch.empty(K * Dp + K, dtype=torch.float32, device=dev) for _ in range(2)]   # [sums | counts]
+            gsums = [p[: K * Dp] for p in part]
+            gcounts = [p[K * Dp:] for p in part]
+            sync = torch.cuda.Event.synchronize
 
-        def launch(it):
-            """enqueue iteration `it` (E-step, M-step, averaging) and the async read-back of its status word"""
-            sl = it & 1
-            Cin, Cout = Cb[it % 3], Cb[(it + 1) % 3]
-            lab, lab_old = Lb[it % 3], Lb[(it + 2) % 3]            # (it - 1) % 3
-            if it == 0:
-                k.cnorm(Cin, cnorm[0])                             # later norms / permuted centres come out of finalize
-                if perm:
-                    k.permute_k8(Cin, Cp[0])
-            if bf and perm and not self._sharded and hasattr(k, "lloyd_step_bf16"):
-                k.lloyd_step_bf16(Xc, Xp, Xb, xnb, Cin, Cimg, cnorm[it % 3], lab, lab_old, n_changed[sl], gsums[sl], gcounts[sl],
-                                  Cout, Cp[(it + 1) % 3], cnorm[(it + 1) % 3], shift, status[sl], bstats, **sph)
+            def launch(it):
+                """enqueue iteration `it` (one fused call: E-step, M-step, averaging) and the async read-back of its status word"""
+                sl = it & 1
+                estep(Cb[it % 3], Cp[it % 3], cnorm[it % 3], Lb[it % 3], Lb[(it + 2) % 3], n_changed[sl], gsums[sl], gcounts[sl],
+                      Cb[(it + 1) % 3], Cp[(it + 1) % 3], cnorm[(it + 1) % 3], shift, status[sl], **sph)
                 read_back(sl)
-                return
-            if perm and not self._sharded and hasattr(k, "lloyd_step"):
-                k.lloyd_step(Xc, Xp, Cin, Cp[it % 3], cnorm[it % 3], lab, lab_old, n_changed[sl], gsums[sl], gcounts[sl],
-                             Cout, Cp[(it + 1) % 3], cnorm[(it + 1) % 3], shift, status[sl], **sph)
-                read_back(sl)
-                return
-            if self._sharded:
+        else:
+            PL = K * Dp + K + 2                                          # [sums | counts | n_changed lo, hi]
+            payload = [torch.empty(1, PL, dtype=ex.dtype, device=dev) for _ in range(2)]
+            # reduced in place, or gathered into one row per rank
+            parts = payload if ex.n_parts == 1 else [torch.empty(ex.n_parts, PL, dtype=ex.dtype, device=dev) for _ in range(2)]
+            gsums = [torch.empty(K * Dp, dtype=torch.float32, device=dev) for _ in range(2)]
+            gcounts = [torch.empty(K, dtype=torch.float32, device=dev) for _ in range(2)]
+            sync = ex.sync
+
+            def launch(it):
+                """enqueue iteration `it` (local half, the ONE collective, global half) and the async read-back of its status word"""
+                sl = it & 1
                 # two foreign calls around the iteration's ONE collective.  A rank whose local half raises (an allocation that fails, a bad
                 # argument) must still ENTER the collective, or its peers wait for it until the process group's timeout: it contributes a
                 # POISONED payload — the n_changed high slot, which a healthy rank fills with < 2^11 — from then on, and raises the cause
                 # where the loop reads that iteration's status; its peers see the poison in the same status word and raise there too.
                 if not local_failure:
                     try:
-                        if bf:
-                            k.lloyd_local_bf16(Xc, Xp, Xb, xnb, Cin, Cimg, cnorm[it % 3], lab, lab_old, payload[sl], bstats)
-                        else:
-                            k.lloyd_local(Xc, Xp if perm else None, Cin, Cp[it % 3], cnorm[it % 3], lab, lab_old, payload[sl])
+                        estep(Cb[it % 3], Cp[it % 3], cnorm[it % 3], Lb[it % 3], Lb[(it + 2) % 3], payload[sl])
                     except Exception as e:                              # noqa: BLE001 — re-raised by read() of this iteration
                         local_failure.append((it, e))
                 if local_failure:
                     payload[sl].zero_()
                     payload[sl].view(-1)[-1] = _POISON
-                if self.exchange == "oneshot":
-                    call("slic_allreduce_oneshot_f64", oneshot, ptr(payload[sl]), payload[sl].numel(), stream())
-                elif self.exchange == "allreduce" and comm is not None:
-                    call("slic_allreduce_f64", comm, ptr(payload[sl]), payload[sl].numel(), stream())
-                elif self._host_staged(payload[sl]):
-                    if self.exchange == "allreduce":
-                        h = payload[sl].cpu()
-                        torch.distributed.all_reduce(h, group=self.process_group)
-                        payload[sl].copy_(h)
-                    else:
-                        parts[sl].copy_(self._gather(payload[sl].view(-1)).view_as(parts[sl]))
-                elif self.exchange == "allreduce":
-                    torch.distributed.all_reduce(payload[sl], group=self.process_group)
-                else:
-                    torch.distributed.all_gather_into_tensor(parts[sl].view(-1), payload[sl].view(-1), group=self.process_group)
+                ex.reduce(payload[sl], parts[sl])
                 if local_failure:
                     return          # no global half, no read-back: read() of the failed iteration raises (the loop runs one launch ahead of
                                     # its reads, so this rank keeps entering the collectives its peers enter until they all get there)
-                k.lloyd_global(parts[sl], Cin, gsums[sl], gcounts[sl], Cout, Cp[(it + 1) % 3], cnorm[(it + 1) % 3], shift,
+                k.lloyd_global(parts[sl], Cb[it % 3], gsums[sl], gcounts[sl], Cb[(it + 1) % 3], Cp[(it + 1) % 3], cnorm[(it + 1) % 3], shift,
                                status[sl], **sph)
                 read_back(sl)
-                return
-            n_changed[sl].zero_()
-            if bf:
-                k.assign_bf16(Xc, Xb, xnb, Cin, k.bf16_image(Cin)[0], cnorm[it % 3], lab, lab_old, n_changed[sl], bstats)
-            elif perm:
-                k.assign_perm(Xp, Cp[it % 3], cnorm[it % 3], lab, lab_old, n_changed[sl])
-            else:
-                k.assign(Xc, Cin, cnorm[it % 3], lab, lab_old, n_changed[sl])
-            k.accumulate(Xc, lab, K, part[sl][: K * Dp], part[sl][K * Dp:])
-            k.finalize(Cin, gsums[sl], gcounts[sl], Cout, shift, n_changed[sl], status[sl], cnorm[(it + 1) % 3],
-                       *((Cp[(it + 1) % 3],) if perm else ()), **sph)
-            read_back(sl)
 
         def read(it):
             if local_failure and local_failure[0][0] <= it:
                 raise local_failure[0][1]
             if on_gpu:
-                if comm is not None:
-                    # bounded: a peer that never joined the iteration's all-reduce aborts the communicator and raises here.  The wait is on
-                    # THIS iteration's event (recorded behind its collective and status read-back): iteration it + 1, already enqueued,
-                    # keeps running ahead, and the deadline covers one iteration
-                    call("slic_comm_wait_event", comm, ctypes.c_void_p(ev[it & 1].cuda_event), comm_timeout_ms())
-                ev[it & 1].synchronize()
-                if self._sharded and self.exchange == "oneshot":
-                    # the exchange kernel never hangs: a wait that ran out (a lost peer) is recorded and surfaces here
-                    call("slic_oneshot_check", oneshot)
+                sync(ev[it & 1])                                            # bounded where the exchange is the library's own
             st = host[it & 1].tolist()
-            if self._sharded and st[2] >= _POISON:                      # n_changed = low + 2^20 * high: a peer's poisoned high slot
+            if ex is not None and st[2] >= _POISON:                     # n_changed = low + 2^20 * high: a peer's poisoned high slot
                 raise _lib.SlicError("sharded k-means: a peer's local half of the Lloyd iteration failed (it raised the cause); "
                                      "every rank leaves the fit here instead of waiting in the next collective")
             return st
@@ -704,6 +552,9 @@ class KMeans:
             torch.cuda.synchronize(dev)
         t_loop = time.time()                                               # the Lloyd phase proper (SURVEY.md §8d metric 2)
         if self.max_iter > 0:
+            k.cnorm(Cb[0], cnorm[0])                                       # later norms / permuted centres come out of the iterations
+            if k.uses_perm:
+                k.permute_k8(Cb[0], Cp[0])
             launch(0)
         while it < self.max_iter:
             speculated = it + 1 < self.max_iter
@@ -717,7 +568,7 @@ class KMeans:
                 if self._relocate(Xc, Cb[it % 3], Lb[it % 3], gsums[sl], gcounts[sl], int(n_empty)):
                     n_reloc += 1
                     k.finalize(Cb[it % 3], gsums[sl], gcounts[sl], Cb[(it + 1) % 3], shift, n_changed[sl], status[sl],
-                               cnorm[(it + 1) % 3], *((Cp[(it + 1) % 3],) if perm else ()), **sph)
+                               cnorm[(it + 1) % 3], Cp[(it + 1) % 3], **sph)
                     shift_tot = status[sl].cpu().tolist()[0]
                     if speculated:
                         launch(it + 1)
@@ -743,9 +594,9 @@ class KMeans:
             cn = cnorm[(last + 1) % 3] if self.max_iter > 0 else cnorm[0]
             if self.max_iter <= 0:
                 k.cnorm(C, cn)
-            if bf:
+            if Xb is not None:
                 k.assign_bf16(Xc, Xb, xnb, C, k.bf16_image(C)[0], cn, out, None, None, bstats)
-            elif perm and self.max_iter > 0:
+            elif k.uses_perm and self.max_iter > 0:
                 k.assign_perm(Xp, Cp[(last + 1) % 3], cn, out, None, None)
             else:
                 k.assign(Xc, C, cn, out, None, None)
@@ -757,34 +608,9 @@ class KMeans:
         return res
 
     def _side_stream(self, dev):
-        if getattr(self, "_side", None) is None:
+        if self._side is None:
             self._side = torch.cuda.Stream(device=dev)
         return self._side
-
-    def _row_norms(self, Xc):
-        """squared row norms of the (centred) data, cached like the permuted copy"""
-        key = (Xc.data_ptr(), tuple(Xc.shape), Xc._version)
-        if getattr(self, "_norm_key", None) != key:
-            xn = torch.empty(Xc.shape[0], dtype=torch.float32, device=Xc.device)
-            self.k.cnorm(Xc, xn)
-            self._norm_key, self._norm_X = key, xn
-        return self._norm_X
-
-    def _bf16_image(self, Xc):
-        """bf16 image and row norms of the (centred) data for the bf16 E-step; cached while Xc is the same tensor"""
-        key = (Xc.data_ptr(), tuple(Xc.shape), Xc._version)
-        if getattr(self, "_img_key", None) != key:
-            self._img_key, self._img = key, self.k.bf16_image(Xc, want_norms=True)
-        return self._img
-
-    def _permuted(self, Xc):
-        """k-permuted copy of the (centred) data for the LDS-DMA E-step; cached while Xc is the same tensor"""
-        key = (Xc.data_ptr(), tuple(Xc.shape), Xc._version)
-        if getattr(self, "_perm_key", None) != key:
-            Xp = torch.empty_like(Xc)
-            self.k.permute_k8(Xc, Xp)
-            self._perm_key, self._perm_X = key, Xp
-        return self._perm_X
 
     def _inertia(self, Xc, C, labels):
         N = Xc.shape[0]
@@ -792,16 +618,11 @@ class KMeans:
         out = torch.empty(1, dtype=torch.float64, device=Xc.device)
         self.k.dist_to_assigned(Xc, C, labels, dist)
         self.k.sum_f64(dist, out)
-        if self._sharded:
-            tot = 0.0
-            for v in self._gather(out).cpu().numpy().reshape(-1):
-                tot += float(v)
-            return tot
-        return float(out.item())
+        return float(self._rank_sum(out)[0])
 
     def _relocate(self, Xc, C_old, labels, gsums, gcounts, n_empty):
         """_relocate_empty_clusters_dense (_k_means_common.pyx:167-211).  Returns False when max(dist) == 0."""
-        k = self.k
+        k, ex = self.k, self._ex
         N, Dp = Xc.shape
         dev = Xc.device
         n_sel = n_empty
@@ -816,13 +637,13 @@ class KMeans:
         xfar = Xc.index_select(0, fi)
         old_ids = labels.index_select(0, fi)
         fd = torch.where(valid, far_dist, torch.full_like(far_dist, -1.0))
-        if self._sharded:
+        if ex is not None:
             # merge the per-rank candidates by (dist desc, global row asc), keep n_empty
             gidx = fi + self._row0
-            fdh = self._gather(fd).reshape(-1).cpu().numpy()
-            gih = self._gather(gidx).reshape(-1).cpu().numpy()
-            allx = self._gather(xfar).reshape(-1, Dp)
-            allold = self._gather(old_ids).reshape(-1)
+            fdh = ex.gather(fd).reshape(-1).cpu().numpy()
+            gih = ex.gather(gidx).reshape(-1).cpu().numpy()
+            allx = ex.gather(xfar).reshape(-1, Dp)
+            allold = ex.gather(old_ids).reshape(-1)
             order = np.lexsort((gih, -fdh))[:n_empty]
             order = order[fdh[order] >= 0]
             sel = torch.from_numpy(order).to(dev)
@@ -839,99 +660,44 @@ class KMeans:
         return True
 
     # ------------------------------------------------------------------ k-means++
-    def _kmeans_plusplus_all(self, Xc, K, R):
-        """the k-means++ seeding of ALL R initialisations of the n_init loop at once, or None when the lock-step kernel does not
-        apply (then the loop seeds run by run).  sklearn's loop draws, per run, the first row and then (K - 1) x T uniforms from
-        ONE RNG stream; neither depends on the data, and Lloyd draws nothing, so the draws are made here in that order and the R
-        runs — independent of each other from then on — take each step as one pass over X (slic_kmeanspp_run_batch)."""
-        k = self.k
-        T = 2 + int(np.log(K))
-        if (self._sharded or not hasattr(k, "kpp_run_batch") or not getattr(k, "uses_perm", False) or T > 16 or R * T > 160
-                or os.environ.get("SLIC_KPP_BATCH", "1") == "0"):
-            return None
-        N, Dp = Xc.shape
-        if N * Xc.stride(0) * 4 >= (1 << 31):
-            return None
-        dev = Xc.device
-        rs = self._rng()
-        firsts, us = [], []
-        for _ in range(R):
-            firsts.append(int(rs.choice(N, p=np.full(N, 1.0 / N))))
-            us.append(rs.uniform(size=(K - 1, T)) if K > 1 else np.zeros((0, T)))
-        ud = torch.from_numpy(np.ascontiguousarray(np.stack(us, 0), dtype=np.float64)).to(dev)
-        idx_d = torch.empty(R, K, dtype=torch.int32, device=dev)
-        k.kpp_run_batch(self._permuted(Xc), self._row_norms(Xc), firsts, K, T, ud, idx_d)
-        ih = idx_d.cpu().numpy().astype(np.int64)
-        self.init_indices_log_ = [ih[r] for r in range(R)]          # every run's picks (the sequential loop appends run by run)
-        self.init_indices_ = ih[-1]
-        return [Xc.index_select(0, idx_d[r].long()).contiguous() for r in range(R)]
-
-    def _kmeans_plusplus(self, Xc, K):
-        """_kmeans_plusplus (_kmeans.py:174-277): RNG draws on the host from numpy's legacy RandomState (as
-        sklearn), distances / potentials / cumsum-search on the device.  In sharded runs every rank seeds on the
-        all-gathered matrix and follows rank 0's draws (identical centres everywhere)."""
-        k = self.k
-        if self._sharded:
-            W = len(self._sizes)
-            mx = int(self._sizes.max())
-            if int(self._sizes.min()) == mx:
-                Xs = self._gather(Xc).reshape(-1, Xc.shape[1]).contiguous()
-            else:
-                pad = torch.zeros(mx, Xc.shape[1], dtype=Xc.dtype, device=Xc.device)
-                pad[: Xc.shape[0]] = Xc
-                allp = self._gather(pad)
-                Xs = torch.cat([allp[r, : int(self._sizes[r])] for r in range(W)], 0).contiguous()
-        else:
-            Xs = Xc
-        N, Dp = Xs.shape
+    def _kmeans_plusplus(self, seed, K, R):
+        """_kmeans_plusplus (_kmeans.py:174-277) for the R runs of the n_init loop, as a generator: run r's initial centres (rows of
+        the centred matrix) are made when run r asks for them.  RNG draws on the host from numpy's legacy RandomState (as sklearn):
+        per run the first row, then (K - 1) x T uniforms, all from ONE stream.  They do not depend on the data and Lloyd draws nothing,
+        so a run's draws are made up front and its K - 1 steps (distances, potentials, cumsum-search) run back to back on the device
+        (kpp_run) — or, where the lock-step kernel applies, the draws of ALL runs are made in that order at the first request and the
+        R seedings take each step as one pass over X (kpp_run_batch).  In sharded runs every rank seeds on the all-gathered matrix
+        and follows rank 0's draws (identical centres everywhere)."""
+        k, ex = self.k, self._ex
+        Xs, Xsp, xn = seed
+        N = Xs.shape[0]
         dev = Xs.device
         rs = self._rng()
-        T = 2 + int(np.log(K))
-        newdist = torch.empty(T, N, dtype=torch.float32, device=dev)
-        closest = torch.empty(N, dtype=torch.float32, device=dev)
-        pot = torch.empty(T, dtype=torch.float64, device=dev)
-        cand = torch.zeros(T, dtype=torch.int32, device=dev)
-        vals = torch.empty(T, dtype=torch.float64, device=dev)
-        idx = np.full(K, -1, np.int64)
+        T = _kpp_trials(K)
 
-        def bcast(a):
-            if not self._sharded:
-                return a
-            t = torch.from_numpy(np.ascontiguousarray(a))
-            t = t if torch.distributed.get_backend(self.process_group) == "gloo" else t.to(dev)
-            src = torch.distributed.get_global_rank(self.process_group, 0)
-            torch.distributed.broadcast(t, src, group=self.process_group)
-            return t.cpu().numpy()
+        def draw():
+            first = np.array([rs.choice(N, p=np.full(N, 1.0 / N))], np.int64)
+            u = rs.uniform(size=(K - 1, T)) if K > 1 else np.zeros((0, T))
+            return (int(first[0]), u) if ex is None else (int(ex.bcast(first, dev)[0]), ex.bcast(u, dev) if K > 1 else u)
 
-        first = int(bcast(np.array([rs.choice(N, p=np.full(N, 1.0 / N))], np.int64))[0])
-        if hasattr(k, "kpp_run") and T <= 16:
-            # the RNG draws of the loop below do not depend on the data: draw them all now (same stream, same order),
-            # and let the device run the K - 1 steps back to back
-            u = bcast(rs.uniform(size=(K - 1, T))) if K > 1 else np.zeros((0, T))
-            ud = torch.from_numpy(np.ascontiguousarray(u, dtype=np.float64)).to(dev)
-            idx_d = torch.empty(K, dtype=torch.int32, device=dev)
-            Xp = xn = None
-            if getattr(k, "uses_perm", False):
-                Xp = self._permuted(Xs)                      # the same permuted copy the E-step uses (cached per fit)
-                xn = self._row_norms(Xs)
-            k.kpp_run(Xs, first, K, T, ud, idx_d, Xp, xn)
-            self.init_indices_ = idx_d.cpu().numpy().astype(np.int64)
-            self.init_indices_log_.append(self.init_indices_)
-            return Xs.index_select(0, idx_d.long()).contiguous()
-        idx[0] = first
-        cand[0] = first
-        k.kpp_step(Xs, cand, 1, None, closest, pot)
-        cur_pot = float(pot[0].item())
-        for c in range(1, K):
-            rv = bcast(rs.uniform(size=T)) * cur_pot
-            vals.copy_(torch.from_numpy(rv))
-            k.cumsum_search(closest, vals, T, cand)
-            k.kpp_step(Xs, cand, T, closest, newdist, pot)
-            ph = pot.cpu().numpy()
-            b = int(np.argmin(ph))
-            cur_pot = float(ph[b])
-            closest.copy_(newdist[b])
-            idx[c] = int(cand[b].item())
-        self.init_indices_ = idx
-        self.init_indices_log_.append(idx)
-        return Xs.index_select(0, torch.from_numpy(idx).to(dev)).contiguous()
+        def on_device(u):
+            return torch.from_numpy(np.ascontiguousarray(u, dtype=np.float64)).to(dev)
+
+        lockstep = (R > 1 and ex is None and k.kpp_run_batch is not None and R * T <= 160 and N * Xs.stride(0) * 4 < (1 << 31)
+                    and os.environ.get("SLIC_KPP_BATCH", "1") != "0")
+        if lockstep:
+            draws = [draw() for _ in range(R)]
+            idx_d = torch.empty(R, K, dtype=torch.int32, device=dev)
+            k.kpp_run_batch(Xsp, xn, [f for f, _ in draws], K, T, on_device(np.stack([u for _, u in draws], 0)), idx_d)
+            ih = idx_d.cpu().numpy().astype(np.int64)
+        for r in range(R):
+            if lockstep:
+                idx, picks = idx_d[r], ih[r]
+            else:
+                first, u = draw()
+                idx = torch.empty(K, dtype=torch.int32, device=dev)
+                k.kpp_run(Xs, first, K, T, on_device(u), idx, Xsp, xn)
+                picks = idx.cpu().numpy().astype(np.int64)
+            self.init_indices_ = picks
+            self.init_indices_log_.append(picks)                    # every run's picks
+            yield Xs.index_select(0, idx.long()).contiguous()
