@@ -525,7 +525,9 @@ int slic_pair_distance_bwd(const float* X, const float* Y, const float* g, int n
                            void* stream);
 /* LLC margin term of triplet_train_epoch (online_train.py:317-332): loss = mean_i max(0, (1 - cos(x_i, y_i)) -
  * (1 - cos(x_i, z_i)) + margin)  (MarginRankingLoss with target -1 on the two cosine distances).
- * state: [n, 8] floats kept for bwd; rowloss: [n] scratch.  bwd: gradients to all three inputs. */
+ * state: [n][8] floats kept for bwd = {cos(x,y), cos(x,z), |x|, |y|, |z| (each norm clamped at 1e-8), active (1 where the hinge
+ * argument is > 0, else 0), two unused}; the euclidean form keeps {d1, d2, -, -, -, active, -, -}; unused slots are not written.
+ * rowloss: [n] scratch.  bwd: gradients to all three inputs (exactly 0 for a row whose hinge argument is <= 0). */
 int slic_margin_cos_fwd(const float* X, const float* Y, const float* Z, int n, int D, float margin, float* state,
                         float* rowloss, float* loss, void* stream);
 int slic_margin_cos_bwd(const float* X, const float* Y, const float* Z, const float* state, int n, int D,
@@ -545,7 +547,10 @@ int slic_ntxent_euclid_bwd(const float* E, const float* dist, const float* wm, i
 /* negative selection of NegativeTripletSelector.get_one_one_triplets (loss/triplet_loss.py:311-360) for P (anchor,
  * positive) pairs over the [n, n] distance matrix `dist`: mode 0 random_negative, 1 random_semi_hard, 2 fixed_semi_hard;
  * u[P] uniform in [0,1) stands in for Python's random.choice (unused for mode 2); fallback = hardest easy negative,
- * returned as its position in the negatives list exactly like the reference.  labels: int64 [n]. */
+ * returned as its position in the negatives list exactly like the reference.  labels: int64 [n], compared as 64-bit.
+ * The contract on u is [0, 1) (torch.rand); the rank is floor(u * count) evaluated in float32 (count converted to float, one
+ * rounded product), in ascending column order, and a product that rounds up to count is taken as count - 1.  Ties of the
+ * arg-max (mode 2) and of the closest negative (fallback) go to the lowest column. */
 int slic_triplet_select(const float* dist, const int64_t* labels, int n, const int32_t* anchors,
                         const int32_t* positives, int P, float margin, int mode, const float* u, int32_t* negatives,
                         void* stream);
@@ -567,7 +572,8 @@ int slic_pdist(const float* V, int n, int D, float eps, int euclidean, float* ou
 int slic_pdist2(const float* X, int nx, const float* Y, int ny, int D, float eps, int euclidean, float* out, void* stream);
 /* InfoNCE over gathered rows ('all_semi_hard', loss/triplet_loss.py:118-203): X [P, D] anchors, Y [P, NY, D] with row 0 the
  * positive and rows 1..NY-1 the picked negatives (NY <= 8): loss = mean_i -log(e^{cos(x,y0)/T} / sum_j e^{cos(x,yj)/T}).
- * state [P][18] floats is kept for the backward, which returns dX [P, D] and dY [P, NY, D] scaled by *gscale. */
+ * state [P][18] floats = {cos_0 .. cos_7, |y_0| .. |y_7|, |x|, sum_j e^{cos_j/T}} (norms clamped at 1e-8; the slots of j >= NY are
+ * not written) is kept for the backward, which returns dX [P, D] and dY [P, NY, D] scaled by *gscale. */
 int slic_infonce_rows_fwd(const float* X, const float* Y, int P, int NY, int D, float temperature, float* state,
                           float* rowloss, float* loss, void* stream);
 int slic_infonce_rows_bwd(const float* X, const float* Y, const float* state, int P, int NY, int D, float temperature,
