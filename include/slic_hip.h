@@ -98,7 +98,9 @@ int slic_sum_f32_to_f64(const float* v, int64_t N, double* out, void* workspace,
  * run can merge candidates across GPUs in between:
  *  select_far: the n_sel farthest rows by (dist descending, ties -> lower row); dist is clobbered.
  *              (sklearn: np.argpartition(distances, -n_empty)[:-n_empty-1:-1]; identical for
- *              n_empty == 1, introselect-order-dependent above that.)
+ *              n_empty == 1, introselect-order-dependent above that.)  A taken row's dist becomes -2, every other entry
+ *              stays.  Only a distance that compares greater than -1 can be taken, so a NaN never is; when such rows
+ *              run out (n_sel > N, NaNs) the remaining entries are far_idx = N and far_dist = -1.  N < 2^31.
  *  apply_relocation: for e = 0..n-1 in order: sums[old_ids[e]] -= xfar[e]; sums[new_ids[e]] = xfar[e];
  *              counts[new] = 1; counts[old] -= 1.   xfar: [n, D] rows (stride ldf). */
 int slic_kmeans_select_far(float* dist, int64_t N, int n_sel, int32_t* far_idx, float* far_dist,
@@ -112,7 +114,12 @@ int slic_kmeans_apply_relocation(const float* xfar, int ldf, const int32_t* old_
  * ||C_new_j - C_old_j||; cnorm_new (optional, [K]) = slic_kmeans_cnorm(C_new), so the next E-step needs no extra
  * launch.  status (device double[4]) = { sum_j shift[j]^2, number of clusters with
  * counts == 0, *n_changed (or -1 if NULL), 0 } — the one word the host loop reads per iteration
- * (_kmeans.py:717-731).  C_new must not alias sums or C_old. */
+ * (_kmeans.py:717-731).  C_new must not alias sums or C_old.
+ * The biggest cluster is the FIRST maximum of counts (np.argmax); an empty cluster j copies its row — the mean when it
+ * precedes j, the raw sum otherwise.  With every count zero that is cluster 0 unscaled: every row of C_new is sums[0].
+ * shift[j] = sqrtf(groups of four squared differences, each added left to right, groups ascending, then the D % 4 tail),
+ * every product and sum rounded on its own (no fused multiply-add); status[0] adds shift[j]^2 in double over a fixed
+ * partition (thread t of 256: j = t, t + 256, ...) and a fixed binary tree. */
 int slic_kmeans_finalize(const float* C_old, const float* sums, const float* counts, int K, int D,
                          float* C_new, float* shift /* [K] */, float* cnorm_new /* [K] or NULL */,
                          float* C_new_perm /* [K][D] in slic_kmeans_permute_k8 order, or NULL */,
@@ -257,12 +264,15 @@ int slic_sub_rowvec(const float* X, int64_t N, int D, int ldx, const float* v, f
                     int ldo, void* stream);
 
 /* out[i,:] = X[i,:] / ||X[i,:]||_2   (preprocess_features_kmeans, cluster_masks.py:30-34;
- * no epsilon, like the reference) */
+ * no epsilon, like the reference): out = x / float32(sqrt(sum of x^2 in double)), a true division.  An all-zero row
+ * gives 0 / 0: a row of NaN, as torch's x / x.norm() does.  Any D and strides >= D. */
 int slic_l2norm_rows(const float* X, int64_t N, int D, int ldx, float* out, int ldo, void* stream);
 
 /* k-means++ helper (_kmeans.py:236-264): for T candidate rows cand[t] of X,
  * newdist[t,i] = min(closest[i], ||x_i - x_cand[t]||^2) and pot[t] = sum_i newdist[t,i] (double).
- * If T == 1 and closest == NULL: newdist[0,i] = ||x_i - x_cand||^2 (first centre). */
+ * If closest == NULL (the first centre, T == 1; any T is taken): newdist[t,i] = ||x_i - x_cand[t]||^2.
+ * The squared distance is the k-ascending fmaf chain of (x_i - x_cand[t])^2 (slic_kmeans_dist_to_assigned's chain); the
+ * order of pot's double sum is not fixed.  1 <= T <= 16, D % 4 == 0, ldx >= D, T * D * 4 <= 64 KiB, 0 < N < 2^31. */
 size_t slic_kmeanspp_step_workspace_bytes(int64_t N, int T);
 int slic_kmeanspp_step(const float* X, int64_t N, int D, int ldx, const int32_t* cand, int T,
                        const float* closest, float* newdist, double* pot, void* workspace,
@@ -289,7 +299,9 @@ int slic_kmeanspp_run_batch(const float* Xp, const float* xnorm, int64_t N, int 
                             const double* uniforms, int32_t* idx_out, void* workspace, void* stream);
 
 /* inclusive prefix sum of v (float) in double, and searchsorted(cumsum, vals[t], 'left')
- * clipped to N-1  (stable_cumsum + np.searchsorted, _kmeans.py:243-248). */
+ * clipped to N-1  (stable_cumsum + np.searchsorted, _kmeans.py:243-248).  'left': the FIRST index whose prefix sum
+ * reaches vals[t] (>=), so a value equal to a prefix sum that a run of zeros repeats gives the run's first row, and
+ * vals[t] <= 0 gives 0; a value above the total gives N - 1 (the clip).  N < 2^31, T > 0. */
 size_t slic_cumsum_search_workspace_bytes(int64_t N);
 int slic_cumsum_search(const float* v, int64_t N, const double* vals, int T, int32_t* idx_out,
                        void* workspace, void* stream);

@@ -1226,7 +1226,9 @@ __global__ __launch_bounds__(256) void kpp_dist(const float* __restrict__ X, int
                                                 const float* __restrict__ closest,
                                                 float* __restrict__ newdist,
                                                 double* __restrict__ bpart /* [nblk][T] */) {
-  extern __shared__ float cs[];  // [T][D] candidate rows
+  extern __shared__ double kpp_lds[];         // [4][PP_TMAX] wave potentials, then [T][D] candidate rows (floats)
+  double (*wp)[PP_TMAX] = (double (*)[PP_TMAX])kpp_lds;
+  float* cs = (float*)(kpp_lds + 4 * PP_TMAX);
   for (int e = threadIdx.x; e < T * D; e += blockDim.x) {
     const int t = e / D, k = e - t * D;
     cs[e] = X[(int64_t)cand[t] * ldx + k];
@@ -1261,7 +1263,6 @@ __global__ __launch_bounds__(256) void kpp_dist(const float* __restrict__ X, int
       }
   }
   // block potentials (double, wave shuffle then LDS)
-  __shared__ double wp[4][PP_TMAX];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
   for (int t = 0; t < PP_TMAX; ++t) {
@@ -1795,6 +1796,7 @@ static int km_assign_perm_impl(const float* Xp, int64_t N, int D, int ldx, const
                                                                               best_score, nullptr);
     if (bc) {
       SLIC_LAUNCH_CHECK();
+      if ((size_t)K * 4 > 48 * 1024) SLIC_LDS_LIMIT(km_block_hist, (size_t)K * 4);
       km_block_hist<<<dim3((unsigned)slic_cdiv(N, KM_SB)), dim3(KM_SB), (size_t)K * 4, st>>>(labels, N, K, bc);
     }
   }
@@ -1861,6 +1863,7 @@ static int km_accumulate_impl(const float* X, int64_t N, int D, int ldx, const i
     return SLIC_OK;
   }
   if (!have_hist) {
+    if ((size_t)K * 4 > 48 * 1024) SLIC_LDS_LIMIT(km_block_hist, (size_t)K * 4);
     km_block_hist<<<dim3(nblk), dim3(KM_SB), (size_t)K * 4, st>>>(labels, N, K, bc);
     SLIC_LAUNCH_CHECK();
   }
@@ -1907,8 +1910,8 @@ extern "C" int slic_kmeans_combine_shards(const float* ps, const float* pc, int6
 extern "C" int slic_kmeans_dist_to_assigned(const float* X, int64_t N, int D, int ldx,
                                             const float* C, int ldc, const int32_t* labels,
                                             float* dist, void* stream) {
-  SLIC_REQUIRE(X && C && labels && dist && N > 0 && D > 0 && D % 4 == 0 && ldx % 4 == 0 && ldc % 4 == 0,
-               "slic_kmeans_dist_to_assigned: bad args (D %% 4 == 0 required)");
+  SLIC_REQUIRE(X && C && labels && dist && N > 0 && D > 0 && D % 4 == 0 && ldx % 4 == 0 && ldc % 4 == 0 && ldx >= D && ldc >= D,
+               "slic_kmeans_dist_to_assigned: bad args (D %% 4 == 0, ldx >= D, ldc >= D required)");
   km_dist_to_assigned<<<dim3((unsigned)slic_cdiv(N, 256)), dim3(256), 0, S_(stream)>>>(X, N, D, ldx, C, ldc, labels, dist);
   SLIC_LAUNCH_CHECK();
   return SLIC_OK;
@@ -1930,6 +1933,7 @@ extern "C" int slic_sum_f32_to_f64(const float* v, int64_t N, double* out, void*
 extern "C" int slic_kmeans_select_far(float* dist, int64_t N, int n_sel, int32_t* far_idx,
                                       float* far_dist, void* stream) {
   SLIC_REQUIRE(dist && far_idx && far_dist && N > 0 && n_sel > 0, "slic_kmeans_select_far: bad args");
+  SLIC_REQUIRE(N < (1ll << 31), "slic_kmeans_select_far: N too large for int32 row ids");
   km_select_far<<<dim3(1), dim3(1024), 0, S_(stream)>>>(dist, N, n_sel, far_idx, far_dist);
   SLIC_LAUNCH_CHECK();
   return SLIC_OK;
@@ -2065,8 +2069,8 @@ extern "C" int slic_col_stats(const float* X, int64_t N, int D, int ldx, double*
 
 extern "C" int slic_sub_rowvec(const float* X, int64_t N, int D, int ldx, const float* v, float* out,
                                int ldo, void* stream) {
-  SLIC_REQUIRE(X && v && out && N > 0 && D > 0 && D % 4 == 0 && ldx % 4 == 0 && ldo % 4 == 0,
-               "slic_sub_rowvec: bad args (D %% 4 == 0 required)");
+  SLIC_REQUIRE(X && v && out && N > 0 && D > 0 && D % 4 == 0 && ldx % 4 == 0 && ldo % 4 == 0 && ldx >= D && ldo >= D,
+               "slic_sub_rowvec: bad args (D %% 4 == 0, ldx >= D, ldo >= D required)");
   const int64_t tot = N * (D / 4);
   sub_rowvec<<<dim3((unsigned)slic_cdiv(tot, 256)), dim3(256), 0, S_(stream)>>>(X, N, D / 4, ldx, v, out, ldo);
   SLIC_LAUNCH_CHECK();
@@ -2087,10 +2091,14 @@ extern "C" int slic_kmeanspp_step(const float* X, int64_t N, int D, int ldx, con
                                   int T, const float* closest, float* newdist, double* pot,
                                   void* workspace, void* stream) {
   SLIC_REQUIRE(X && cand && newdist && pot && workspace, "slic_kmeanspp_step: null pointer");
-  SLIC_REQUIRE(T >= 1 && T <= PP_TMAX && D % 4 == 0 && ldx % 4 == 0 && (size_t)T * D * 4 <= 64 * 1024,
-               "slic_kmeanspp_step: need 1 <= T <= %d, D %% 4 == 0, T*D*4 <= 64 KiB", PP_TMAX);
+  SLIC_REQUIRE(T >= 1 && T <= PP_TMAX && D > 0 && D % 4 == 0 && ldx % 4 == 0 && ldx >= D && (size_t)T * D * 4 <= 64 * 1024,
+               "slic_kmeanspp_step: need 1 <= T <= %d, D %% 4 == 0, ldx >= D, T*D*4 <= 64 KiB", PP_TMAX);
+  SLIC_REQUIRE(N > 0 && N < (1ll << 31), "slic_kmeanspp_step: need 0 < N < 2^31 (N=%lld)", (long long)N);
   const int64_t nblk = slic_cdiv(N, 256);
-  kpp_dist<<<dim3((unsigned)nblk), dim3(256), (size_t)T * D * 4, S_(stream)>>>(X, N, D, ldx, cand, T, closest, newdist, (double*)workspace);
+  // the candidate rows and, in front of them, the kernel's 4 x PP_TMAX wave potentials: all of the kernel's LDS is in this one block
+  const size_t lds = (size_t)T * D * 4 + 4 * PP_TMAX * sizeof(double);
+  if (lds > 48 * 1024) SLIC_LDS_LIMIT(kpp_dist, lds);
+  kpp_dist<<<dim3((unsigned)nblk), dim3(256), lds, S_(stream)>>>(X, N, D, ldx, cand, T, closest, newdist, (double*)workspace);
   SLIC_LAUNCH_CHECK();
   kpp_pot<<<dim3(T), dim3(256), 0, S_(stream)>>>((const double*)workspace, nblk, T, pot);
   SLIC_LAUNCH_CHECK();
@@ -2205,6 +2213,7 @@ extern "C" size_t slic_cumsum_search_workspace_bytes(int64_t N) {
 extern "C" int slic_cumsum_search(const float* v, int64_t N, const double* vals, int T,
                                   int32_t* idx_out, void* workspace, void* stream) {
   SLIC_REQUIRE(v && vals && idx_out && workspace && N > 0 && T > 0, "slic_cumsum_search: bad args");
+  SLIC_REQUIRE(N < (1ll << 31), "slic_cumsum_search: N too large for int32 indices");
   const int64_t nc = slic_cdiv(N, 1024);
   cs_chunk_sums<<<dim3((unsigned)nc), dim3(256), 0, S_(stream)>>>(v, N, (double*)workspace);
   SLIC_LAUNCH_CHECK();
