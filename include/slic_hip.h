@@ -825,6 +825,24 @@ int slic_dropout_fwd(const float* x, int64_t n, float p, uint64_t seed, uint64_t
 int slic_dropout_bwd(const float* dy, int64_t n, float p, uint64_t seed, uint64_t offset, float* dx, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Segment means for the downstream protocol (coclr_classify.py:575, 622 softmax(logit).mean(0) per view, then the mean over views; :734
+ * feature.mean(0)).  x: R rows of C fp32 values, row pitch ld >= C (elements).  The rows fall into V consecutive segments,
+ * [seg_off[v], seg_off[v + 1]); for each
+ *   table[rows[v]][0 .. C)  (accumulate ? += : =)  w[v] * sum over the segment's rows r, ascending, of f(x_r)
+ * with f the identity (mode 0) or the softmax over the C columns (mode 1: expf(x - rowmax) / sum of them).  Every output is ONE
+ * sequential fp32 sum in ascending r, compensated (the rounding error of every addition is summed beside it and added at the end,
+ * unless it is not finite); w[v] * sum is rounded, then added: no float atomics, the same inputs give the same bits.
+ * Rows of table that no segment addresses, and its columns C .. ldt, are not touched.
+ * segs: {int32 seg_off[V + 1], int32 rows[V], float w[V]} packed in that order, on the device; segs_host: the same bytes on the
+ * host, which the entry point checks before it launches anything: 0 <= seg_off[0], seg_off ascending with no empty segment,
+ * seg_off[V] <= R, rows[] distinct and inside [0, table_rows), 1 <= C <= 4096, ld and ldt >= C, mode and accumulate 0 or 1, R, V,
+ * table_rows >= 1 — SLIC_EINVAL otherwise (answers without a device).
+ * Non-finite inputs propagate as IEEE arithmetic does (a NaN, a +inf, or a row of nothing but -inf gives NaN in that segment's
+ * row), except that a -inf logit beside a finite row maximum contributes exactly 0 in mode 1. */
+int slic_segment_mean(const float* x, int64_t ld, int R, int C, const void* segs, const void* segs_host, int V, int mode,
+                      int accumulate, float* table, int64_t ldt, int table_rows, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * MoCo queue contrast (loss/NCE_loss.py MemoryMoCo :188-241; the InfoNCE / UberNCE loss of online_train.py:96-97): queries q [B, D]
  * and keys k [B, D] against a dense queue memory [K, D], all row-major fp32, 1 <= D <= 512, K D < 2^29.
  *   logit[b, 0] = <q_b, k_b> / T,  logit[b, 1 + j] = <memory_j, q_b> / T

@@ -11,6 +11,8 @@ path behind the reference's Python call surface (rvl-lab-utoronto/video_similari
                                             <- evaluate.py:208-307, iic_retrieve_clips.py:275-314
     evaluate.k_nearest_embeddings           <- evaluate.py:353-400 (plot=False)
     validation.validate                     <- validation.py:12-151
+    coclr_classify.train_one_epoch / validate / test_10crop / test_retrieval
+                                            <- coclr_classify.py:395-830
     misc.distributed_helper                 <- misc/distributed_helper.py
 
 All arithmetic runs in hand-written HIP kernels in csrc/ behind the C ABI of include/slic_hip.h

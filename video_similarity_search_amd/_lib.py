@@ -181,6 +181,8 @@ SIGNATURES = {
     "slic_softmax_ce_bwd": (I, [P, L, P, P, I, I, P, P, P]),
     "slic_dropout_fwd": (I, [P, L, F, ctypes.c_uint64, ctypes.c_uint64, P, P]),
     "slic_dropout_bwd": (I, [P, L, F, ctypes.c_uint64, ctypes.c_uint64, P, P]),
+    # downstream protocol: segment means of rows / of their softmax
+    "slic_segment_mean": (I, [P, L, I, I, P, P, I, I, I, P, L, I, P]),
     # MoCo queue contrast
     "slic_moco_logits_fwd": (I, [P, P, P, I, I, I, F, P, P]),
     "slic_moco_logits_bwd": (I, [P, P, P, I, I, I, F, P, P, P]),

@@ -1,2 +1,3 @@
-"""the reference's coclr_utils package: the tensor clip transforms (transforms.py)"""
+"""the reference's coclr_utils package: the tensor clip transforms (transforms.py) and the meters / loaders of utils.py (imported on
+demand: `from video_similarity_search_amd.coclr_utils.utils import AverageMeter`)"""
 from . import transforms  # noqa: F401

@@ -17,6 +17,11 @@ transforms return new tensors, never views.
 
 5-D input [B, 3, N, H, W] is accepted by hflip / RandomHorizontalFlip and Normalize(channel=1) only, as coclr_classify.py uses them;
 everything else on a 5-D tensor raises ValueError: use Compose.batch.
+
+Test-time views (coclr_classify.py:540-556): FiveCrop, RandomHorizontalFlip(command=), and multi_view(clip, composes), which runs n
+chains on ONE source clip as one launch; ten_crop_views lists the ten chains of the ten-crop protocol.  Two departures there: the
+resample to img_dim is this module's bilinear (the reference's A.Scale is PIL bicubic on uint8 images), and the reference's
+test-time ColorJitter(.., p=0.3), a random perturbation of an evaluation, is not applied.
 """
 import math
 import numbers
@@ -670,6 +675,38 @@ class CenterCrop:
         return center_crop(vid, self.size)
 
 
+class FiveCrop:
+    """one of the five windows of coclr_utils/augmentation.py:64-90: where = 1 top-left, 2 top-right, 3 bottom-left, 4 bottom-right,
+    5 centre.  Window 4 starts at row h - tw and is tw rows high, as the reference's box (w - tw, h - tw, w, h) is: the same window
+    as the other three corners for a square size, a tw x tw one otherwise."""
+    _plans = True
+
+    def __init__(self, size, where=1):
+        self.size = (int(size), int(size)) if isinstance(size, numbers.Number) else tuple(size)
+        if where not in (1, 2, 3, 4, 5):
+            raise ValueError(f"FiveCrop: where is 1 .. 5, not {where!r}")
+        self.where = where
+
+    def window(self, h, w):
+        """(i, j, rows, columns) of the window inside an h x w frame"""
+        th, tw = self.size
+        if th > h or tw > w:
+            raise ValueError("Requested crop size {} is bigger than input size {}".format(self.size, (h, w)))
+        if self.where == 1:
+            return 0, 0, th, tw
+        if self.where == 2:
+            return 0, w - tw, th, tw
+        if self.where == 3:
+            return h - th, 0, th, tw
+        if self.where == 4:
+            return h - tw, w - tw, tw, tw
+        return int(round((h - th) / 2.)), int(round((w - tw) / 2.)), th, tw
+
+    def __call__(self, vid):
+        h, w = vid.shape[-2:]
+        return crop(vid, *self.window(h, w))
+
+
 class Resize:
     _plans = True
 
@@ -707,10 +744,14 @@ class Normalize:
 
 
 class RandomHorizontalFlip:
+    """command='left' never flips and command='right' always does (coclr_utils/augmentation.py:152-169, the forced forms of
+    coclr_classify.py's test-time views); the draw is still made, as there"""
     _plans = True
 
-    def __init__(self, p=0.5):
-        self.p = p
+    def __init__(self, p=0.5, command=None):
+        if command not in (None, 'left', 'right'):
+            raise ValueError(f"RandomHorizontalFlip: command is 'left', 'right' or None, not {command!r}")
+        self.p = 0 if command == 'left' else 1 if command == 'right' else p
 
     def __call__(self, vid):
         if random.random() < self.p:
@@ -788,3 +829,39 @@ class ColorJitter:
 
     def __repr__(self):
         return f"{self.__class__.__name__}(brightness={self.brightness}, contrast={self.contrast}, saturation={self.saturation})"
+
+
+# Views of one clip (coclr_classify.py:540-556: the test-time crops and flips)
+
+def multi_view(clip, composes, *, kernels=None):
+    """torch.stack([c(clip) for c in composes]) — parameters drawn chain by chain in that order — from ONE source clip: the per-clip
+    records of a launch carry their own source pointer, so the n records share it.  One parameter upload and the launches of one
+    Compose.batch when every chain folds into one group of one output shape; contiguous float32 [n_views, 3, N, H, W]."""
+    composes = list(composes)
+    if not composes:
+        raise ValueError("multi_view: no views")
+    progs = []
+    for c in composes:
+        if not isinstance(c, Compose):
+            raise TypeError("multi_view takes Compose chains")
+        progs.append(c.plan(Program(clip, kernels if kernels is not None else c.kernels)))
+    if any(p.five_d for p in progs):
+        raise ValueError("multi_view takes one 4-D clip")
+    return _execute(progs[0].kern, [p.clips[0] for p in progs])
+
+
+def ten_crop_views(crop, out, *, kernels=None):
+    """the ten chains of coclr_classify.py's ten-crop test for a uint8 [N, H, W, 3] clip, in its order: centre, top-left, top-right,
+    bottom-left, bottom-right unflipped, then the same five flipped (the flip comes before the window, as there).  Each is
+    [0, 1] scaling, RandomHorizontalFlip(command=), FiveCrop(crop, where) and a bilinear resize to `out` (left out when the window
+    already has that size).  The first chain alone is the centre-crop protocol, the first five the five-crop one."""
+    crop = (int(crop), int(crop)) if isinstance(crop, numbers.Number) else tuple(int(v) for v in crop)
+    out = (int(out), int(out)) if isinstance(out, numbers.Number) else tuple(int(v) for v in out)
+    chains = []
+    for command in ('left', 'right'):
+        for where in (5, 1, 2, 3, 4):
+            chain = [ToFloatTensorInZeroOne(), RandomHorizontalFlip(command=command), FiveCrop(crop, where)]
+            if out != crop:
+                chain.append(Resize(out))
+            chains.append(Compose(chain, kernels=kernels))
+    return chains
