@@ -61,9 +61,10 @@ def case(name):
 
 
 @contextlib.contextmanager
-def recording(env=None):
+def recording(env=None, label=None):
     """for the duration of the block every int-returning entry point of the loaded library appends its name to the yielded list
-    (_lib.call and the direct callers all look the names up on that one library object); `env` is set for the block too"""
+    (_lib.call and the direct callers all look the names up on that one library object); `env` is set for the block too.
+    label(name, args), when given, returns what is appended instead of the bare name"""
     from video_similarity_search_amd import _lib
     lib = _lib.load()
     seq = []
@@ -72,7 +73,7 @@ def recording(env=None):
 
     def wrapper(n, f):
         def w(*a):
-            seq.append(n)
+            seq.append(n if label is None else label(n, a))
             return f(*a)
         return w
     try:

@@ -124,6 +124,40 @@ def _grad_out(p):
     return torch.empty_like(p, memory_format=torch.contiguous_format)
 
 
+def _bias_grad(d2, p):
+    """gradient of the bias p of a linear layer whose output gradient is d2 [B, features]: its column sums"""
+    g = _grad_out(p)
+    call("slic_colsum", ptr(d2), d2.shape[0], d2.shape[1], ptr(g), stream())
+    return g
+
+
+class _WgradStream:
+    """the weight gradients of one seg_backward call: on `side` when there is one (beside the main stream's work), else on main"""
+    def __init__(self, main, side, B):
+        self.main, self.side, self.B = main, side, B
+
+    def wgrad(self, plan, x, dz, weight):
+        if not weight.requires_grad:
+            return None
+        dW = _grad_out(weight)                      # allocated on the main stream: it outlives the side stream's use
+        if self.side is None:
+            return plan.wgrad(x, dz, self.B, dW)
+        ev = torch.cuda.Event()
+        ev.record(self.main)
+        self.side.wait_event(ev)
+        for t in (x, dz, dW):
+            t.record_stream(self.side)              # the caching allocator must not recycle them under the side kernel
+        with torch.cuda.stream(self.side):
+            plan.wgrad(x, dz, self.B, dW)
+        return dW
+
+    def join(self):
+        if self.side is not None:
+            ev = torch.cuda.Event()
+            ev.record(self.side)
+            self.main.wait_event(ev)
+
+
 class _Engine:
     """Execution plan of one ResNet at one input shape: conv plans (tables on the device), forward and backward
     passes written out layer by layer.  Mirrors ResNet.forward / BasicBlock.forward of the reference
@@ -240,7 +274,7 @@ class _Engine:
         y = y.view(B, self.n_pad)
         return y if self.n_pad == self.n_cls else y[:, :self.n_cls]
 
-    def _classify_bwd(self, ctx, dy, need_dx, new_like):
+    def _classify_bwd(self, ctx, dy, need_dx):
         """returns (gradient wrt the pooled features or None, {parameter: gradient})"""
         lin = self.linear_mod
         B = dy.shape[0]
@@ -251,7 +285,7 @@ class _Engine:
         d5 = dy.view(B, 1, 1, 1, self.n_pad)
         grads = {}
         if lin.weight.requires_grad:               # a frozen weight launches no weight gradient
-            gw = new_like(lin.weight)
+            gw = _grad_out(lin.weight)
             if self.n_pad == self.n_cls:
                 self.lin.wgrad(ctx["xin"].view(B, 1, 1, 1, self.feat), d5, B, gw)
             else:
@@ -259,15 +293,13 @@ class _Engine:
                 self.lin.wgrad(ctx["xin"].view(B, 1, 1, 1, self.feat), d5, B, gwp)
                 gw.copy_(gwp[:self.n_cls])
             grads[lin.weight] = gw
-        if lin.bias.requires_grad:
-            gb = new_like(lin.bias)
-            if self.n_pad == self.n_cls:
-                call("slic_colsum", ptr(dy), B, self.n_pad, ptr(gb), stream())
-            else:
-                gbp = torch.empty(self.n_pad, dtype=torch.float32, device=dy.device)
-                call("slic_colsum", ptr(dy), B, self.n_pad, ptr(gbp), stream())
-                gb.copy_(gbp[:self.n_cls])
-            grads[lin.bias] = gb
+        if lin.bias.requires_grad and self.n_pad == self.n_cls:
+            grads[lin.bias] = _bias_grad(dy, lin.bias)
+        elif lin.bias.requires_grad:
+            gb = grads[lin.bias] = _grad_out(lin.bias)
+            gbp = torch.empty(self.n_pad, dtype=torch.float32, device=dy.device)
+            call("slic_colsum", ptr(dy), B, self.n_pad, ptr(gbp), stream())
+            gb.copy_(gbp[:self.n_cls])
         if not need_dx:
             return None, grads
         dpool = self.lin.dgrad(d5, self.lin.pack_dgrad(ctx["lin_w"]), B).view(B, self.feat)
@@ -441,22 +473,22 @@ class _Engine:
             mods = [net.linear] if net.classifier else [net.fc1, net.bn_proj, net.fc2] if net.projection_head else []
         return [p for m in mods for p in m.parameters() if p.requires_grad]
 
-    def _conv_bn_act(self, plan, inp, weight, bnmod, res, relu, training, B, keep=False):
-        """conv -> BN -> (+res) -> relu; returns (z or None, y, bn).  keep: an eval-mode pass whose backward will run — the
+    def _conv_bn_act(self, plan, inp, weight, bnmod, res, relu, training, B, keep=False, bias=None):
+        """conv (+bias) -> BN -> (+res) -> relu; returns (z or None, y, bn).  keep: an eval-mode pass whose backward will run — the
         BatchNorm is applied unfolded on its running statistics, z is kept"""
         bn = _Bn(bnmod)
         wp = plan.pack_fwd(weight)
         if not training and keep:
-            z, _ = plan.forward(inp, wp, B)
+            z, _ = plan.forward(inp, wp, B, bias=bias)
             self._bn_frozen(bn)
             return z, self._apply(z, bn, res, relu), bn
         if training:
-            z, part = plan.forward(inp, wp, B, want_stats=True)
+            z, part = plan.forward(inp, wp, B, bias=bias, want_stats=True)
             self._bn_train(bn, part, z.numel() // bn.C)
             y = self._apply(z, bn, res, relu)
             return z, y, bn
-        self._bn_eval(bn)                     # eval: BN folded into the conv epilogue
-        y, _ = plan.forward(inp, wp, B, scale=bn.scale, shift=bn.shift, addend=res, relu=relu)
+        self._bn_eval(bn)                     # eval: bias first, then the BN affine, then ReLU — all folded into the conv epilogue
+        y, _ = plan.forward(inp, wp, B, bias=bias, scale=bn.scale, shift=bn.shift, addend=res, relu=relu)
         return None, y, bn
 
     def seg_forward(self, si, inp, training, save):
@@ -468,7 +500,12 @@ class _Engine:
             pend.clear()
         self._nbt = []
         try:
-            out = self._seg_forward(si, inp, training, save)
+            if si == 0:
+                out = self._stem_forward(inp, training, save)
+            elif si < self.N_SEG - 1:
+                out = self._layer_forward(si, inp, training, save)
+            else:
+                out = self._head_forward(inp, training, save)
         except BaseException:
             # a forward that aborts after some BatchNorm layers have updated their running statistics: their counters are bumped NOW, so that a
             # checkpoint written from the handler agrees with its own running statistics (the reference bumps inside each BatchNorm forward)
@@ -493,77 +530,68 @@ class _Engine:
             torch._foreach_add_(pend, 1)
             pend.clear()
 
-    def _seg_forward(self, si, inp, training, save):
+    def _stem_forward(self, inp, training, save):
         net = self.net
         B = inp.shape[0]
-        dev = inp.device
-        if si == 0:
-            x4 = self.stem.make_source(inp)          # NCDHW clip -> the stem plan's operand layout (W-run for RGB)
-            z0, a, bn0 = self._conv_bn_act(self.stem, x4, net.conv1.weight, net.bn1, None, True, training, B, keep=save)
-            if self.pool_in is None:
-                return a, (dict(x4=x4, z0=z0, a0=a, bn0=bn0) if save else None)
-            T, H, W = self.pool_in
-            C = a.shape[-1]
-            pooled = torch.empty((B,) + tuple((d - 1) // 2 + 1 for d in self.pool_in) + (C,), dtype=torch.float32, device=dev)
-            arg = torch.empty(pooled.shape, dtype=torch.int32, device=dev) if save else None
-            call("slic_maxpool3d_fwd", ptr(a), B, T, H, W, C, ptr(pooled), ptr(arg), stream())
-            return pooled, (dict(x4=x4, z0=z0, a0=a, bn0=bn0, pool_arg=arg) if save else None)
+        x4 = self.stem.make_source(inp)          # NCDHW clip -> the stem plan's operand layout (W-run for RGB)
+        z0, a, bn0 = self._conv_bn_act(self.stem, x4, net.conv1.weight, net.bn1, None, True, training, B, keep=save)
+        if self.pool_in is None:
+            return a, (dict(x4=x4, z0=z0, a0=a, bn0=bn0) if save else None)
+        T, H, W = self.pool_in
+        C = a.shape[-1]
+        pooled = torch.empty((B,) + tuple((d - 1) // 2 + 1 for d in self.pool_in) + (C,), dtype=torch.float32, device=inp.device)
+        arg = torch.empty(pooled.shape, dtype=torch.int32, device=inp.device) if save else None
+        call("slic_maxpool3d_fwd", ptr(a), B, T, H, W, C, ptr(pooled), ptr(arg), stream())
+        return pooled, (dict(x4=x4, z0=z0, a0=a, bn0=bn0, pool_arg=arg) if save else None)
+
+    def _layer_forward(self, si, inp, training, save):
         self._await_packs()
-        if si <= 4:
-            a = inp
-            saved = []
-            for blk, p1, p2, pd in self.layer_blocks[si - 1]:
-                xin = a
-                p3 = self.p3.get(blk)
-                z1, a1, b1 = self._conv_bn_act(p1, xin, blk.conv1.weight, blk.bn1, None, True, training, B, keep=save)
-                if p3 is not None:
-                    z2, a2, b2 = self._conv_bn_act(p2, a1, blk.conv2.weight, blk.bn2, None, True, training, B, keep=save)
-                if pd is not None:
-                    zd, r, bd = self._conv_bn_act(pd, xin, blk.downsample[0].weight, blk.downsample[1], None, False, training, B, keep=save)
-                elif blk in self.short_a:
-                    stride, planes = self.short_a[blk]
-                    T, H, W = p1.in_dims
-                    r = torch.empty((B,) + tuple((p3 or p2).out_dims) + (planes,), dtype=torch.float32, device=dev)
-                    call("slic_shortcut_a", ptr(xin), B, T, H, W, xin.shape[-1], stride, planes, ptr(r), stream())
-                    zd, bd = None, None
-                else:
-                    zd, r, bd = None, xin, None
-                if p3 is not None:
-                    z3, out, b3 = self._conv_bn_act(p3, a2, blk.conv3.weight, blk.bn3, r, True, training, B, keep=save)
-                    if save:     # zl / bl: the block's LAST convolution output and BatchNorm (what the layer above fuses into its dgrad)
-                        saved.append(dict(x=xin, z1=z1, a1=a1, b1=b1, z2=z2, a2=a2, b2=b2, z3=z3, b3=b3, out=out, zd=zd, bd=bd, zl=z3, bl=b3))
-                else:
-                    z2, out, b2 = self._conv_bn_act(p2, a1, blk.conv2.weight, blk.bn2, r, True, training, B, keep=save)
-                    if save:
-                        saved.append(dict(x=xin, z1=z1, a1=a1, b1=b1, z2=z2, out=out, b2=b2, zd=zd, bd=bd, zl=z2, bl=b2))
-                a = out
-            return a, (dict(blocks=saved) if save else None)
-        # head: pool -> fc2(relu(bn_proj(fc1(x))))   (models/resnet.py:286-299), or pool -> dropout -> linear with classifier=True (:305-307)
+        B = inp.shape[0]
         a = inp
+        saved = []
+        for blk, p1, p2, pd in self.layer_blocks[si - 1]:
+            xin = a
+            p3 = self.p3.get(blk)
+            z1, a1, b1 = self._conv_bn_act(p1, xin, blk.conv1.weight, blk.bn1, None, True, training, B, keep=save)
+            if p3 is not None:
+                z2, a2, b2 = self._conv_bn_act(p2, a1, blk.conv2.weight, blk.bn2, None, True, training, B, keep=save)
+            if pd is not None:
+                zd, r, bd = self._conv_bn_act(pd, xin, blk.downsample[0].weight, blk.downsample[1], None, False, training, B, keep=save)
+            elif blk in self.short_a:
+                stride, planes = self.short_a[blk]
+                T, H, W = p1.in_dims
+                r = torch.empty((B,) + tuple((p3 or p2).out_dims) + (planes,), dtype=torch.float32, device=inp.device)
+                call("slic_shortcut_a", ptr(xin), B, T, H, W, xin.shape[-1], stride, planes, ptr(r), stream())
+                zd, bd = None, None
+            else:
+                zd, r, bd = None, xin, None
+            if p3 is not None:
+                z3, out, b3 = self._conv_bn_act(p3, a2, blk.conv3.weight, blk.bn3, r, True, training, B, keep=save)
+                if save:     # zl / bl: the block's LAST convolution output and BatchNorm (what the layer above fuses into its dgrad)
+                    saved.append(dict(x=xin, z1=z1, a1=a1, b1=b1, z2=z2, a2=a2, b2=b2, z3=z3, b3=b3, out=out, zd=zd, bd=bd, zl=z3, bl=b3))
+            else:
+                z2, out, b2 = self._conv_bn_act(p2, a1, blk.conv2.weight, blk.bn2, r, True, training, B, keep=save)
+                if save:
+                    saved.append(dict(x=xin, z1=z1, a1=a1, b1=b1, z2=z2, out=out, b2=b2, zd=zd, bd=bd, zl=z2, bl=b2))
+            a = out
+        return a, (dict(blocks=saved) if save else None)
+
+    def _head_forward(self, inp, training, save):
+        """pool -> fc2(relu(bn_proj(fc1(x))))   (models/resnet.py:286-299), or pool -> dropout -> linear with classifier=True (:305-307)"""
+        self._await_packs()
+        net = self.net
+        B = inp.shape[0]
         To, Ho, Wo = self.final_dims
         S = To * Ho * Wo
-        pooled = torch.empty(B, self.feat, dtype=torch.float32, device=dev)
-        call("slic_avgpool_fwd", ptr(a), B, S, self.feat, ptr(pooled), stream())
-        ctx = dict(last_shape=tuple(a.shape), pooled=pooled) if save else None
+        pooled = torch.empty(B, self.feat, dtype=torch.float32, device=inp.device)
+        call("slic_avgpool_fwd", ptr(inp), B, S, self.feat, ptr(pooled), stream())
+        ctx = dict(last_shape=tuple(inp.shape), pooled=pooled) if save else None
         if net.classifier:
             return self._classify(pooled, training, ctx), ctx
         if not net.projection_head:
             return pooled, ctx
-        bnp = _Bn(net.bn_proj)
-        w1 = self.fc1.pack_fwd(net.fc1.weight)
-        p5 = pooled.view(B, 1, 1, 1, self.feat)
-        if training:
-            h1, part = self.fc1.forward(p5, w1, B, bias=net.fc1.bias, want_stats=True)
-            self._bn_train(bnp, part, B)
-            ah = self._apply(h1, bnp, None, True)
-        elif save:             # eval mode with a backward to come: unfolded, on the running statistics
-            h1, _ = self.fc1.forward(p5, w1, B, bias=net.fc1.bias)
-            self._bn_frozen(bnp)
-            ah = self._apply(h1, bnp, None, True)
-        else:
-            self._bn_eval(bnp)
-            h1 = None      # bias first, then the BN affine, then ReLU — all in the epilogue
-            ah, _ = self.fc1.forward(p5, w1, B, bias=net.fc1.bias, scale=bnp.scale, shift=bnp.shift, relu=True)
+        h1, ah, bnp = self._conv_bn_act(self.fc1, pooled.view(B, 1, 1, 1, self.feat), net.fc1.weight, net.bn_proj, None, True, training, B,
+                                        keep=save, bias=net.fc1.bias)
         w2 = self.fc2.pack_fwd(net.fc2.weight)
         y, _ = self.fc2.forward(ah.view(B, 1, 1, 1, -1), w2, B, bias=net.fc2.bias)
         if save:
@@ -579,20 +607,9 @@ class _Engine:
         """returns (gradient wrt the segment input or None, {parameter: gradient}); pid = forward pass the context is from.
         need_dinp (segment 0): the clip requires a gradient — the NCDHW gradient is computed and returned.  A weight with
         requires_grad == False launches no weight gradient (a saliency pass on a frozen encoder pays for data gradients only)."""
-        net = self.net
-        grads = {}
-        B = dout.shape[0]
         dout = dout.contiguous()
         self._await_packs()
-
         _GRAD_VIEWS[0] = getattr(self, "grad_views", None)
-        new_like = _grad_out
-
-        def bias_grad(d2, p):
-            g = new_like(p)
-            call("slic_colsum", ptr(d2), d2.shape[0], d2.shape[1], ptr(g), stream())
-            return g
-
         # Weight gradients on a side stream: they depend only on (saved activation, dz), nothing downstream in this segment
         # depends on them, and they are MFMA-bound — so they overlap the HBM-bound BatchNorm passes and fill the partial
         # last rounds of the data-gradient launches; the main stream joins before returning.  All segments: +1.3 % clips/s
@@ -602,169 +619,151 @@ class _Engine:
         # side-stream kernel overlaps, and reports the overlapped data-gradient launches beside them).  "0": off.
         mode = os.environ.get("SLIC_WGRAD_STREAM", "1")
         side = self._side_stream() if (mode == "1" or (mode == "auto" and si != 1)) else None
-        main = torch.cuda.current_stream()
+        wg = _WgradStream(torch.cuda.current_stream(), side, dout.shape[0])
+        if si == self.N_SEG - 1:
+            return self._head_backward(ctx, dout)           # launches nothing on the side stream: no join
+        res = self._stem_backward(ctx, dout, pid, need_dinp, wg) if si == 0 else self._layer_backward(si, ctx, dout, pid, wg)
+        wg.join()
+        return res
 
-        def wgrad_async(plan, x, dz, weight):
-            if not weight.requires_grad:
+    def _head_backward(self, ctx, dy):
+        net = self.net
+        grads = {}
+        B = dy.shape[0]
+        need_dx = ctx.get("need_dx", True)
+        if net.classifier:
+            dpool, grads = self._classify_bwd(ctx, dy, need_dx)
+            if not need_dx:                    # linear probe: nothing below the head is in the graph
+                return None, grads
+        elif net.projection_head:
+            ah, h1, bnp, pooled = ctx["ah"], ctx["h1"], ctx["bnp"], ctx["pooled"]
+            d5 = dy.view(B, 1, 1, 1, -1)
+            if net.fc2.weight.requires_grad:
+                grads[net.fc2.weight] = self.fc2.wgrad(ah.view(B, 1, 1, 1, -1), d5, B, _grad_out(net.fc2.weight))
+            if net.fc2.bias.requires_grad:
+                grads[net.fc2.bias] = _bias_grad(dy, net.fc2.bias)
+            dah = self.fc2.dgrad(d5, self.fc2.pack_dgrad(net.fc2.weight), B)
+            dh1, _, dg, db = self._bn_bwd(dah.view(B, -1), ah.view(B, -1), h1.view(B, -1), bnp, False)
+            grads[net.bn_proj.weight], grads[net.bn_proj.bias] = dg, db
+            if net.fc1.weight.requires_grad:
+                grads[net.fc1.weight] = self.fc1.wgrad(pooled.view(B, 1, 1, 1, -1), dh1.view(B, 1, 1, 1, -1), B, _grad_out(net.fc1.weight))
+            if net.fc1.bias.requires_grad:
+                grads[net.fc1.bias] = _bias_grad(dh1.view(B, -1), net.fc1.bias)
+            dpool = self.fc1.dgrad(dh1.view(B, 1, 1, 1, -1), self.fc1.pack_dgrad(net.fc1.weight), B).view(B, -1)
+        else:
+            dpool = dy
+        To, Ho, Wo = self.final_dims
+        S = To * Ho * Wo
+        dx = torch.empty(ctx["last_shape"], dtype=torch.float32, device=dy.device)
+        call("slic_avgpool_bwd", ptr(dpool), B, S, self.feat, ptr(dx), stream())
+        return dx, grads
+
+    def _take_prefused(self, pid, si, dout):
+        """the partial sums that travelled beside dout, when the data gradient above already applied this segment's last ReLU mask
+        and took the sums of its BatchNorm backward; else None.  The entry is consumed either way"""
+        pf = self._prefused.pop((pid, si), None)
+        return pf[2] if pf is not None and pf[0] == dout.data_ptr() and pf[1] == tuple(dout.shape) else None
+
+    def _below(self, pid, si, bi, blocks):
+        """(mask, z, bn) of the relu + BatchNorm through which the layer below consumes the dx of block bi (the previous block's bn2,
+        or across the segment boundary the previous segment's last bn2 / the stem's bn1) while its context is alive, else None"""
+        if bi > 0:
+            pb = blocks[bi - 1][1]
+        else:
+            prev = self._live_ctx(pid, si - 1)
+            if prev is None:
                 return None
-            dW = new_like(weight)                       # allocated on the main stream: it outlives the side stream's use
-            if side is None:
-                return plan.wgrad(x, dz, B, dW)
-            ev = torch.cuda.Event()
-            ev.record(main)
-            side.wait_event(ev)
-            for t in (x, dz, dW):
-                t.record_stream(side)                   # the caching allocator must not recycle them under the side kernel
-            with torch.cuda.stream(side):
-                plan.wgrad(x, dz, B, dW)
-            return dW
+            if si - 1 == 0:                    # with the max-pool between, dx does not reach the stem's ReLU directly
+                return (prev["a0"], prev["z0"], prev["bn0"]) if self.pool_in is None else None
+            pb = prev["blocks"][-1]
+        return pb["out"], pb["zl"], pb["bl"]
 
-        def join():
-            if side is not None:
-                ev = torch.cuda.Event()
-                ev.record(side)
-                main.wait_event(ev)
+    def _entry_bn_bwd(self, part, dout, act, z, bn, want_g):
+        """BatchNorm backward where the gradient dout enters a block or the stem, act = relu(bn(z) (+ r)); returns (dz, g, dgamma,
+        dbeta) like _bn_bwd.  part (partial sums, or None): the data gradient that produced dout masked it and took the sums — dout is g"""
+        if part is None:
+            return self._bn_bwd(dout, act, z, bn, want_g)
+        dz, dgamma, dbeta = self._bn_bwd_fused(part, dout, z, bn)
+        return dz, dout, dgamma, dbeta
 
-        if si == 5:
-            dy = dout
-            need_dx = ctx.get("need_dx", True)
-            if net.classifier:
-                dpool, grads = self._classify_bwd(ctx, dy, need_dx, new_like)
-                if not need_dx:                    # linear probe: nothing below the head is in the graph
-                    return None, grads
-            elif net.projection_head:
-                ah, h1, bnp, pooled = ctx["ah"], ctx["h1"], ctx["bnp"], ctx["pooled"]
-                d5 = dy.view(B, 1, 1, 1, -1)
-                if net.fc2.weight.requires_grad:
-                    grads[net.fc2.weight] = self.fc2.wgrad(ah.view(B, 1, 1, 1, -1), d5, B, new_like(net.fc2.weight))
-                if net.fc2.bias.requires_grad:
-                    grads[net.fc2.bias] = bias_grad(dy, net.fc2.bias)
-                dah = self.fc2.dgrad(d5, self.fc2.pack_dgrad(net.fc2.weight), B)
-                dh1, _, dg, db = self._bn_bwd(dah.view(B, -1), ah.view(B, -1), h1.view(B, -1), bnp, False)
-                grads[net.bn_proj.weight], grads[net.bn_proj.bias] = dg, db
-                if net.fc1.weight.requires_grad:
-                    grads[net.fc1.weight] = self.fc1.wgrad(pooled.view(B, 1, 1, 1, -1), dh1.view(B, 1, 1, 1, -1), B, new_like(net.fc1.weight))
-                if net.fc1.bias.requires_grad:
-                    grads[net.fc1.bias] = bias_grad(dh1.view(B, -1), net.fc1.bias)
-                dpool = self.fc1.dgrad(dh1.view(B, 1, 1, 1, -1), self.fc1.pack_dgrad(net.fc1.weight), B).view(B, -1)
+    def _relu_bn_bwd(self, plan, weight, carry, act, z, bn, fuse, B):
+        """One step down a block: act = relu(bn(z)) is the input of the convolution `plan`, carry[0] the gradient at that convolution's
+        output.  Replaces carry[0] by dz and returns (dgamma, dbeta).  fuse: the ReLU mask and the BatchNorm-backward sums ride on the
+        data gradient's epilogue, then _bn_bwd_fused; else plain data gradient, then _bn_bwd.  The slot is emptied as the data gradient is
+        launched and the gradient between the two launches dies with this frame: each is dropped before the next one is allocated"""
+        wd = plan.pack_dgrad(weight)
+        if fuse:
+            g, part = plan.dgrad(carry.pop(), wd, B, mask=act, bwd=(z, bn.mean, bn.invstd))
+            dz, dgamma, dbeta = self._bn_bwd_fused(part, g, z, bn)
+        else:
+            da = plan.dgrad(carry.pop(), wd, B)
+            dz, _, dgamma, dbeta = self._bn_bwd(da, act, z, bn, False)
+        carry.append(dz)
+        return dgamma, dbeta
+
+    def _layer_backward(self, si, ctx, dout, pid, wg):
+        """per block, last first: last BatchNorm -> (conv3 step) -> conv2 step -> conv1's weight gradient -> shortcut -> conv1's data
+        gradient with what lies below on its epilogue -> hand-over to the block or segment below"""
+        grads = {}
+        B = wg.B
+        blocks = list(zip(self.layer_blocks[si - 1], ctx["blocks"]))
+        fuse = os.environ.get("SLIC_BN_FUSE", "1") != "0"
+        part = self._take_prefused(pid, si, dout)     # not None: the dgrad above already produced this block's masked gradient + sums
+        for bi in reversed(range(len(blocks))):
+            (blk, p1, p2, pd), s = blocks[bi]
+            p3 = self.p3.get(blk)
+            # out = relu(bn_l(conv_l(.)) + r), l = the block's last convolution (conv2; conv3 of a Bottleneck)
+            bnl = blk.bn2 if p3 is None else blk.bn3
+            carry = [None]         # the gradient carried down the block lives in this one slot: _relu_bn_bwd takes it out and frees it
+            carry[0], g, grads[bnl.weight], grads[bnl.bias] = self._entry_bn_bwd(part, dout, s["out"], s["zl"], s["bl"], True)
+            if p3 is not None:
+                grads[blk.conv3.weight] = wg.wgrad(p3, s["a2"], carry[0], blk.conv3.weight)
+                # a2 = relu(bn2(conv2(a1))): mask + BatchNorm-backward sums on conv3's dgrad epilogue
+                grads[blk.bn2.weight], grads[blk.bn2.bias] = self._relu_bn_bwd(p3, blk.conv3.weight, carry, s["a2"], s["z2"], s["b2"], fuse, B)
+            grads[blk.conv2.weight] = wg.wgrad(p2, s["a1"], carry[0], blk.conv2.weight)
+            # a1 = relu(bn1(conv1(x))): the ReLU mask and the BatchNorm-backward sums ride on conv2's dgrad epilogue
+            grads[blk.bn1.weight], grads[blk.bn1.bias] = self._relu_bn_bwd(p2, blk.conv2.weight, carry, s["a1"], s["z1"], s["b1"], fuse, B)
+            dz1 = carry.pop()
+            grads[blk.conv1.weight] = wg.wgrad(p1, s["x"], dz1, blk.conv1.weight)
+            below = self._below(pid, si, bi, blocks) if fuse else None        # its mask and sums are fused into conv1's dgrad as well
+            kw = {} if below is None else dict(mask=below[0], bwd=(below[1], below[2].mean, below[2].invstd))
+            if pd is not None:
+                # r = bn_d(conv_d(x)): g is its upstream gradient
+                dzd, _, dgd, dbd = self._bn_bwd(g, None, s["zd"], s["bd"], False)
+                grads[blk.downsample[1].weight], grads[blk.downsample[1].bias] = dgd, dbd
+                grads[blk.downsample[0].weight] = wg.wgrad(pd, s["x"], dzd, blk.downsample[0].weight)
+                # the shortcut's data gradient reaches one input position in stride^3 (1x1x1 kernel): only that parity class is
+                # launched (seven launches that wrote zeros at layer2.0 / 3.0 / 4.0 before), and conv1's data gradient takes dx as
+                # its addend on that class alone — with the same strides the classes of the two plans coincide
+                sparse = pd.stride == p1.stride and pd.stride != (1, 1, 1) and pd.tap_classes() <= p1.tap_classes()
+                dx = pd.dgrad(dzd, pd.pack_dgrad(blk.downsample[0].weight), B, skip_empty=sparse)
+                res = p1.dgrad(dz1, p1.pack_dgrad(blk.conv1.weight), B, addend=dx, out=dx,
+                               addend_classes=pd.tap_classes() if sparse else None, **kw)
+            elif blk in self.short_a:
+                # the reference's shortcut 'A' concatenates `out.data` (models/resnet.py:220): no gradient through the branch
+                res = p1.dgrad(dz1, p1.pack_dgrad(blk.conv1.weight), B, **kw)
             else:
-                dpool = dy
-            To, Ho, Wo = self.final_dims
-            S = To * Ho * Wo
-            dx = torch.empty(ctx["last_shape"], dtype=torch.float32, device=dout.device)
-            call("slic_avgpool_bwd", ptr(dpool), B, S, self.feat, ptr(dx), stream())
-            return dx, grads
-        if si >= 1:
-            blocks = list(zip(self.layer_blocks[si - 1], ctx["blocks"]))
-            fuse = os.environ.get("SLIC_BN_FUSE", "1") != "0"
-            pre = None          # (g, partial) when the previous dgrad already produced this block's masked gradient + sums
-            pf = self._prefused.pop((pid, si), None)
-            if pf is not None and pf[0] == dout.data_ptr() and pf[1] == tuple(dout.shape):
-                pre = (dout, pf[2])
-            for bi in reversed(range(len(blocks))):
-                (blk, p1, p2, pd), s = blocks[bi]
-                p3 = self.p3.get(blk)
-                # out = relu(bn_l(conv_l(.)) + r), l = the block's last convolution (conv2; conv3 of a Bottleneck)
-                if pre is not None:
-                    g, part = pre
-                    dzl, dgl, dbl = self._bn_bwd_fused(part, g, s["zl"], s["bl"])
-                    pre = None
-                else:
-                    dzl, g, dgl, dbl = self._bn_bwd(dout, s["out"], s["zl"], s["bl"], True)
-                if p3 is not None:
-                    grads[blk.bn3.weight], grads[blk.bn3.bias] = dgl, dbl
-                    grads[blk.conv3.weight] = wgrad_async(p3, s["a2"], dzl, blk.conv3.weight)
-                    # a2 = relu(bn2(conv2(a1))): mask + BatchNorm-backward sums on conv3's dgrad epilogue
-                    b2 = s["b2"]
-                    if fuse:
-                        g2, part2 = p3.dgrad(dzl, p3.pack_dgrad(blk.conv3.weight), B, mask=s["a2"], bwd=(s["z2"], b2.mean, b2.invstd))
-                        del dzl
-                        dz2, dg2, db2 = self._bn_bwd_fused(part2, g2, s["z2"], b2)
-                        del g2
-                    else:
-                        da2 = p3.dgrad(dzl, p3.pack_dgrad(blk.conv3.weight), B)
-                        del dzl
-                        dz2, _, dg2, db2 = self._bn_bwd(da2, s["a2"], s["z2"], b2, False)
-                        del da2
-                else:
-                    dz2, dg2, db2 = dzl, dgl, dbl
-                    del dzl
-                grads[blk.bn2.weight], grads[blk.bn2.bias] = dg2, db2
-                grads[blk.conv2.weight] = wgrad_async(p2, s["a1"], dz2, blk.conv2.weight)
-                # a1 = relu(bn1(conv1(x))): the ReLU mask and the BatchNorm-backward sums ride on conv2's dgrad epilogue
-                b1 = s["b1"]
-                if fuse:
-                    g1, part1 = p2.dgrad(dz2, p2.pack_dgrad(blk.conv2.weight), B, mask=s["a1"], bwd=(s["z1"], b1.mean, b1.invstd))
-                    del dz2
-                    dz1, dg1, db1 = self._bn_bwd_fused(part1, g1, s["z1"], b1)
-                    del g1
-                else:
-                    da1 = p2.dgrad(dz2, p2.pack_dgrad(blk.conv2.weight), B)
-                    del dz2
-                    dz1, _, dg1, db1 = self._bn_bwd(da1, s["a1"], s["z1"], b1, False)
-                    del da1
-                grads[blk.bn1.weight], grads[blk.bn1.bias] = dg1, db1
-                grads[blk.conv1.weight] = wgrad_async(p1, s["x"], dz1, blk.conv1.weight)
-                # the layer below consumes dx through relu + BatchNorm (the previous block's bn2, or across the segment
-                # boundary the previous segment's last bn2 / the stem's bn1): fuse its mask and sums as well
-                below = None
-                if fuse and bi > 0:
-                    pb = blocks[bi - 1][1]
-                    below = (pb["out"], pb["zl"], pb["bl"])
-                elif fuse and bi == 0:
-                    prev = self._live_ctx(pid, si - 1)
-                    if prev is not None and si - 1 == 0:
-                        if self.pool_in is None:           # with the max-pool between, dx does not reach the stem's ReLU directly
-                            below = (prev["a0"], prev["z0"], prev["bn0"])
-                    elif prev is not None:
-                        pb = prev["blocks"][-1]
-                        below = (pb["out"], pb["zl"], pb["bl"])
-                kw = {}
-                if below is not None:
-                    kw = dict(mask=below[0], bwd=(below[1], below[2].mean, below[2].invstd))
-                if pd is not None:
-                    # r = bn_d(conv_d(x)): g is its upstream gradient
-                    dzd, _, dgd, dbd = self._bn_bwd(g, None, s["zd"], s["bd"], False)
-                    grads[blk.downsample[1].weight], grads[blk.downsample[1].bias] = dgd, dbd
-                    grads[blk.downsample[0].weight] = wgrad_async(pd, s["x"], dzd, blk.downsample[0].weight)
-                    # the shortcut's data gradient reaches one input position in stride^3 (1x1x1 kernel): only that parity class is
-                    # launched (seven launches that wrote zeros at layer2.0 / 3.0 / 4.0 before), and conv1's data gradient takes dx as
-                    # its addend on that class alone — with the same strides the classes of the two plans coincide
-                    sparse = pd.stride == p1.stride and pd.stride != (1, 1, 1) and pd.tap_classes() <= p1.tap_classes()
-                    dx = pd.dgrad(dzd, pd.pack_dgrad(blk.downsample[0].weight), B, skip_empty=sparse)
-                    res = p1.dgrad(dz1, p1.pack_dgrad(blk.conv1.weight), B, addend=dx, out=dx,
-                                   addend_classes=pd.tap_classes() if sparse else None, **kw)
-                elif blk in self.short_a:
-                    # the reference's shortcut 'A' concatenates `out.data` (models/resnet.py:220): no gradient through the branch
-                    res = p1.dgrad(dz1, p1.pack_dgrad(blk.conv1.weight), B, **kw)
-                else:
-                    res = p1.dgrad(dz1, p1.pack_dgrad(blk.conv1.weight), B, addend=g, **kw)
-                if below is not None and bi > 0:
-                    pre = res
-                    dout = None
-                elif below is not None:
-                    dout, part = res             # crosses the segment boundary through autograd: the sums travel beside it
-                    self._prefused[(pid, si - 1)] = (dout.data_ptr(), tuple(dout.shape), part)
-                else:
-                    dout = res
-            join()
-            return dout, grads
-        # stem: a0 = relu(bn1(conv1(x4))) (-> max-pool); the clip's gradient only when it was asked for (need_dinp)
+                res = p1.dgrad(dz1, p1.pack_dgrad(blk.conv1.weight), B, addend=g, **kw)
+            dout, part = res if below is not None else (res, None)
+        if part is not None:               # crosses the segment boundary through autograd: the sums travel beside it
+            self._prefused[(pid, si - 1)] = (dout.data_ptr(), tuple(dout.shape), part)
+        return dout, grads
+
+    def _stem_backward(self, ctx, dout, pid, need_dinp, wg):
+        """a0 = relu(bn1(conv1(x4))) (-> max-pool); the clip's gradient only when it was asked for (need_dinp)"""
+        net = self.net
+        grads = {}
+        B = wg.B
         if self.pool_in is not None:
             T, H, W = self.pool_in
             da0 = torch.empty_like(ctx["a0"])
             call("slic_maxpool3d_bwd", ptr(dout), ptr(ctx["pool_arg"]), B, T, H, W, da0.shape[-1], ptr(da0), stream())
             dout = da0
-        pf = self._prefused.pop((pid, 0), None)
-        if pf is not None and pf[0] == dout.data_ptr() and pf[1] == tuple(dout.shape):
-            dz0, dg0, db0 = self._bn_bwd_fused(pf[2], dout, ctx["z0"], ctx["bn0"])
-        else:
-            dz0, _, dg0, db0 = self._bn_bwd(dout, ctx["a0"], ctx["z0"], ctx["bn0"], False)
-        grads[net.bn1.weight], grads[net.bn1.bias] = dg0, db0
-        grads[net.conv1.weight] = wgrad_async(self.stem, ctx["x4"], dz0, net.conv1.weight)
+        part = self._take_prefused(pid, 0, dout)
+        dz0, _, grads[net.bn1.weight], grads[net.bn1.bias] = self._entry_bn_bwd(part, dout, ctx["a0"], ctx["z0"], ctx["bn0"], False)
+        grads[net.conv1.weight] = wg.wgrad(self.stem, ctx["x4"], dz0, net.conv1.weight)
         # the transposed stem convolution, on the main stream beside conv1's weight gradient: NCDHW, the clip's own layout
         dinp = self.stem.input_grad(dz0, net.conv1.weight, B) if need_dinp else None
-        join()
         return dinp, grads
 
     # ------------------------------------------------------------------ whole passes (inference, tests, diagnostics)
