@@ -763,6 +763,40 @@ size_t slic_cluster_metrics_workspace_bytes(int64_t N, int64_t max_cells);      
 int slic_cluster_metrics(const int32_t* labels_true, const int32_t* labels_pred, int64_t N, int64_t max_cells, double* record,
                          void* workspace, void* stream);
 
+/* Silhouette coefficient (sklearn.metrics.silhouette_samples / silhouette_score) of rows X [N, D] fp32 (row stride ldx elements, any
+ * alignment) under int32 labels [N] (any values; unit stride), for the two metrics whose sum of distances to a cluster follows from
+ * the cluster's row sum, so that no N x N and no N x K array is built:
+ *   SLIC_SILHOUETTE_COSINE        d(i, j) = 1 - x^_i . x^_j, x^ = x / |x| (a zero row stays zero, as slic_normalize_rows)
+ *   SLIC_SILHOUETTE_SQEUCLIDEAN   d(i, j) = |x_i - x_j|^2
+ * Clusters get dense ids 0 .. K - 1 by ascending label value.  Per cluster the operand rows (x^ resp. x, fp32) are summed in float64
+ * in ascending row order, divided by |C| and rounded once to fp32; |x|^2 is summed in float64 (k ascending), Q_C / |C| likewise.  The
+ * mean distance of row i to cluster C is then, in fp32 with every product-sum an fmaf and the dot product a k-ascending fmaf chain
+ * from +0 (v_mfma_f32_32x32x2_f32),
+ *   cosine: max(1 - x^_i . m_C, 0)        sqeuclidean: max(fmaf(-2, x_i . m_C, |x_i|^2 + Q_C / |C|), 0)
+ * b = the smallest over the OTHER clusters (strict '<': the first dense id wins), a = max(fmaf(|C|, d_own, -self), 0) / (|C| - 1)
+ * with self = 1 - x^_i . x^_i as computed (cosine) resp. 0, s = (b - a) / max(a, b); s = 0 where max(a, b) == 0 and, with a = 0, for
+ * the row of a singleton cluster.  The mean of s over the scored rows and over each cluster is taken in float64 in a fixed order
+ * (strided partial sums, folded by halving): two calls on the same input give the same bits; no floating-point atomics.
+ * has_ignore != 0: rows labelled ignore_label take no part in any quantity; their s, a, b are NaN, their `nearest` is ignore_label.
+ * Outputs (device; each of out_s, out_a, out_b [N] fp32, out_nearest [N] int32 (the nearest other cluster's ORIGINAL label),
+ * cluster_mean [Kmax] float64 and cluster_label [Kmax] int32 may be NULL): cluster_mean[j] / cluster_label[j] describe the j-th scored
+ * cluster by ascending label, slots past K hold NaN / 0.  record (SLIC_SILHOUETTE_RECORD doubles): mean s, K, rows scored, status.
+ * status 0: valid.  SLIC_SILHOUETTE_UNDEFINED: K outside 2 .. rows scored - 1.  SLIC_SILHOUETTE_TOO_MANY: a valid K above Kmax.
+ * With a status every float output is NaN and nearest is 0; nothing faults and the call never synchronises with the host.
+ * Limits: 3 <= N <= SLIC_SILHOUETTE_MAX_N, 1 <= D <= SLIC_SILHOUETTE_MAX_D (padded to D % 8 == 0 inside), 2 <= Kmax <= N - 1;
+ * SLIC_EINVAL beyond.  The workspace (about 4 N (D + 40) + 4 Kmax D bytes) is sized by Kmax, not by the data. */
+#define SLIC_SILHOUETTE_COSINE 0
+#define SLIC_SILHOUETTE_SQEUCLIDEAN 1
+#define SLIC_SILHOUETTE_MAX_N ((int64_t)1 << 24)
+#define SLIC_SILHOUETTE_MAX_D 512
+#define SLIC_SILHOUETTE_RECORD 4
+#define SLIC_SILHOUETTE_UNDEFINED 1
+#define SLIC_SILHOUETTE_TOO_MANY 2
+size_t slic_silhouette_workspace_bytes(int64_t N, int D, int64_t Kmax);          /* 0 for sizes slic_silhouette rejects */
+int slic_silhouette(const float* X, int64_t N, int D, int64_t ldx, const int32_t* labels, int metric, int has_ignore,
+                    int32_t ignore_label, int64_t Kmax, float* out_s, float* out_a, float* out_b, int32_t* out_nearest,
+                    double* record, double* cluster_mean, int32_t* cluster_label, void* workspace, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Memory-bank NCE (loss/NCE_loss.py:26-88 NCEAverage, :341-352 NCESoftmaxLoss): gather + dot + /T without
  * materialising the gathered rows, its backward wrt the features, the momentum bank update, and the

@@ -167,6 +167,9 @@ SIGNATURES = {
     # cluster-quality metrics (NMI / AMI)
     "slic_cluster_metrics_workspace_bytes": (c_size_t, [L, L]),
     "slic_cluster_metrics": (I, [P, P, L, L, P, P, P]),
+    # silhouette coefficient (cosine / sqeuclidean) from per-cluster row sums
+    "slic_silhouette_workspace_bytes": (c_size_t, [L, I, L]),
+    "slic_silhouette": (I, [P, L, I, L, P, I, I, ctypes.c_int32, L, P, P, P, P, P, P, P, P, P]),
     # memory-bank NCE
     "slic_nce_scores_fwd": (I, [P, P, P, I, I, I, F, P, P, P]),
     "slic_nce_scores_bwd": (I, [P, P, P, I, I, I, F, P, P]),

@@ -18,13 +18,13 @@
 //            exp per term; cells are dealt round-robin to 1024 x 256 threads.  The work is sum_ij min(a_i, b_j) terms.
 //   finish   folds the four sets of 1024 partial sums and applies the NMI / AMI rules; writes the record.
 // fp contraction is off for the whole file: a * b + c stays two roundings, which is what the fp64 check restates on the host.
-#include "common.h"
+#include "label_ids.h"
 #include <math.h>
 #include <float.h>
 
 #pragma clang fp contract(off)
 
-#define CM_CHUNK 64           // keys per thread in a radix pass (< 256: the packed counters are bytes)
+#define CM_CHUNK SLIC_LABEL_CHUNK   // keys per thread in a radix pass
 #define CM_G 1024             // workgroups of a fixed-order sum
 #define CM_T 256              // threads per workgroup everywhere but the scan
 #define CM_SCAN_T 1024        // threads of the one-workgroup scan
@@ -32,9 +32,13 @@
 enum { CM_R = 0, CM_C = 1, CM_STATUS = 2, CM_NMETA = 16 };
 enum { CM_P_MI = 0, CM_P_HT = 1, CM_P_HP = 2, CM_P_EMI = 3 };
 
-__global__ __launch_bounds__(CM_T) void cm_keys(const int32_t* __restrict__ labels, int N, uint32_t* __restrict__ keys) {
+// ord (optional): the row numbers the sort carries along
+__global__ __launch_bounds__(CM_T) void cm_keys(const int32_t* __restrict__ labels, int N, uint32_t* __restrict__ keys, int* __restrict__ ord) {
   const int i = blockIdx.x * CM_T + threadIdx.x;
-  if (i < N) keys[i] = (uint32_t)labels[i] ^ 0x80000000u;
+  if (i < N) {
+    keys[i] = (uint32_t)labels[i] ^ 0x80000000u;
+    if (ord) ord[i] = i;
+  }
 }
 
 // hist[d * T + t] = how many keys of thread t's chunk carry digit d
@@ -51,9 +55,12 @@ __global__ __launch_bounds__(CM_T) void cm_radix_hist(const uint32_t* __restrict
   for (int d = 0; d < 16; ++d) hist[d * T + t] = (int)(((d < 8 ? c0 : c1) >> (8 * (d & 7))) & 255ull);
 }
 
-// after the exclusive scan of hist in (digit, thread) order, hist[d * T + t] is where thread t's first key with digit d goes
+// after the exclusive scan of hist in (digit, thread) order, hist[d * T + t] is where thread t's first key with digit d goes.
+// ORD: a payload (the row number) moves with its key; the passes are stable, so equal keys keep their rows ascending.
+template <bool ORD>
 __global__ __launch_bounds__(CM_T) void cm_radix_scatter(const uint32_t* __restrict__ src, uint32_t* __restrict__ dst, int N, int shift,
-                                                        const int* __restrict__ hist, int T) {
+                                                        const int* __restrict__ hist, int T, const int* __restrict__ osrc,
+                                                        int* __restrict__ odst) {
   const int t = blockIdx.x * CM_T + threadIdx.x;
   if (t >= T) return;
   const int lo = t * CM_CHUNK, hi = min(N, lo + CM_CHUNK);
@@ -63,7 +70,10 @@ __global__ __launch_bounds__(CM_T) void cm_radix_scatter(const uint32_t* __restr
     const int d = (int)((key >> shift) & 15u);
     const int seen = (int)(((d < 8 ? c0 : c1) >> (8 * (d & 7))) & 255ull);
     const int at = hist[d * T + t] + seen;
-    if (at >= 0 && at < N) dst[at] = key;
+    if (at >= 0 && at < N) {
+      dst[at] = key;
+      if constexpr (ORD) odst[at] = osrc[k];
+    }
     if (d < 8) c0 += 1ull << (8 * d); else c1 += 1ull << (8 * (d - 8));
   }
 }
@@ -345,23 +355,27 @@ extern "C" size_t slic_cluster_metrics_workspace_bytes(int64_t N, int64_t max_ce
   return cm_layout(nullptr, N, max_cells, nullptr);
 }
 
-// dense ids of one labelling (ascending value), its class sizes, and the class count in *n_uniq
-static int cm_dense_ids(const int32_t* labels, int n, const CmLayout& L, int* ids, int* cnt, int* n_uniq, hipStream_t st) {
+// dense ids of one labelling (ascending value), its class sizes, and the class count in *n_uniq (label_ids.h)
+int slic_label_dense_ids(const int32_t* labels, int n, const SlicLabelScratch& L, int* ids, int* cnt, int* n_uniq, hipStream_t st) {
   const int T = (int)slic_cdiv(n, CM_CHUNK);
   const dim3 gn((unsigned)slic_cdiv(n, CM_T)), gt((unsigned)slic_cdiv(T, CM_T));
-  cm_keys<<<gn, CM_T, 0, st>>>(labels, n, L.keys_a);
+  const bool ord = L.ord_a && L.ord_b;
+  cm_keys<<<gn, CM_T, 0, st>>>(labels, n, L.keys_a, ord ? L.ord_a : nullptr);
   SLIC_LAUNCH_CHECK();
   uint32_t *src = L.keys_a, *dst = L.keys_b;
+  int *osrc = L.ord_a, *odst = L.ord_b;
   for (int shift = 0; shift < 32; shift += 4) {
     cm_radix_hist<<<gt, CM_T, 0, st>>>(src, n, shift, L.hist, T);
     SLIC_LAUNCH_CHECK();
     cm_scan<<<1, CM_SCAN_T, 0, st>>>(L.hist, 16 * T, nullptr);
     SLIC_LAUNCH_CHECK();
-    cm_radix_scatter<<<gt, CM_T, 0, st>>>(src, dst, n, shift, L.hist, T);
+    if (ord) cm_radix_scatter<true><<<gt, CM_T, 0, st>>>(src, dst, n, shift, L.hist, T, osrc, odst);
+    else cm_radix_scatter<false><<<gt, CM_T, 0, st>>>(src, dst, n, shift, L.hist, T, nullptr, nullptr);
     SLIC_LAUNCH_CHECK();
     uint32_t* sw = src; src = dst; dst = sw;
+    int* osw = osrc; osrc = odst; odst = osw;
   }
-  // eight passes: the sorted keys are back in keys_a (= src)
+  // eight passes: the sorted keys are back in keys_a (= src), the rows in ord_a
   cm_heads<<<gn, CM_T, 0, st>>>(src, n, L.pos);
   SLIC_LAUNCH_CHECK();
   cm_scan<<<1, CM_SCAN_T, 0, st>>>(L.pos, n, n_uniq);
@@ -373,6 +387,11 @@ static int cm_dense_ids(const int32_t* labels, int n, const CmLayout& L, int* id
   cm_ids<<<gn, CM_T, 0, st>>>(labels, n, L.uniq, n_uniq, ids);
   SLIC_LAUNCH_CHECK();
   return SLIC_OK;
+}
+
+static int cm_dense_ids(const int32_t* labels, int n, const CmLayout& L, int* ids, int* cnt, int* n_uniq, hipStream_t st) {
+  const SlicLabelScratch S = {L.keys_a, L.keys_b, L.uniq, L.hist, L.pos, L.start, nullptr, nullptr};
+  return slic_label_dense_ids(labels, n, S, ids, cnt, n_uniq, st);
 }
 
 extern "C" int slic_cluster_metrics(const int32_t* labels_true, const int32_t* labels_pred, int64_t N, int64_t max_cells, double* record,

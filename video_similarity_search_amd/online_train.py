@@ -319,8 +319,21 @@ def _cluster_sharded(cfg):
             and cfg.ITERCLUSTER.METHOD in ('kmeans', 'spherical_kmeans') and bool(getattr(cfg.ITERCLUSTER, "SHARDED", True)))
 
 
+def _silhouette_lines(cfg, epoch, embeddings, cluster_labels, kernels):
+    """the opt-in label-free score of the cluster step (cfg.ITERCLUSTER.SILHOUETTE): one print, one line in silhouettes.txt"""
+    from .clustering.metrics import silhouette_score
+    ignore = -1 if cfg.ITERCLUSTER.METHOD == 'DBSCAN' else None                # DBSCAN's noise rows belong to no cluster
+    try:
+        sil = silhouette_score(embeddings, cluster_labels, metric='cosine', ignore_label=ignore, kernels=kernels)
+    except ValueError as e:                     # fewer than 2 clusters, or as many as rows: no score, and no reason to stop training
+        print('Silhouette (cosine) of the cluster assignments: undefined ({})'.format(e))
+        return
+    print('Silhouette (cosine) of the cluster assignments: {:.3f}'.format(sil))
+    _append_log(cfg, 'silhouettes.txt', 'epoch:{} {:.3f}\n'.format(epoch, sil))
+
+
 def iterative_cluster_step(args, cfg, encoder, eval_train_loader, epoch, cuda=True, device=None, is_master_proc=True,
-                           kmeans_kernels=None, metrics_kernels=None):
+                           kmeans_kernels=None, metrics_kernels=None, silhouette_kernels=None):
     """online_train.py:605-662: embeddings of the whole train set -> fit_cluster -> NMI/AMI logs -> vid_clusters.txt in
     the dataset's unshuffled order -> barrier.
 
@@ -337,12 +350,20 @@ def iterative_cluster_step(args, cfg, encoder, eval_train_loader, epoch, cuda=Tr
     as an argument; the product passes nothing and runs the HIP kernels).
     NMI / AMI come from the device (clustering/metrics.py: one call, one record) when `cuda` is true and a device is present, or
     when `metrics_kernels` names a provider; a failure there raises.  With cuda=False and no provider the reference's
-    scikit-learn lines run on the host, and are skipped without scikit-learn as before."""
+    scikit-learn lines run on the host, and are skipped without scikit-learn as before.
+    cfg.ITERCLUSTER.SILHOUETTE (default off; the gathered route only — with the sharded route it raises NotImplementedError before
+    any collective): after the NMI / AMI lines, the cosine silhouette of the assignments (clustering/metrics.py, one device call;
+    DBSCAN's -1 rows ignored) is printed and appended to silhouettes.txt.  It needs a device or `silhouette_kernels`; an undefined
+    score (fewer than 2 clusters, or one per row) prints one line and training goes on."""
     import numpy as np
     from .clustering.cluster_masks import fit_cluster
     from .evaluate import get_embeddings_and_labels
     n_data = len(eval_train_loader.dataset)
     sharded = _cluster_sharded(cfg)
+    want_silhouette = bool(getattr(cfg.ITERCLUSTER, "SILHOUETTE", False))
+    if want_silhouette and sharded:
+        raise NotImplementedError("cfg.ITERCLUSTER.SILHOUETTE is not built for the row-sharded cluster step: every rank holds only "
+                                  "its rows; set ITERCLUSTER.SHARDED = False or leave the flag off")
     if is_master_proc:
         print('\n=> Computing embeddings')
     start_time = time.time()
@@ -432,6 +453,8 @@ def iterative_cluster_step(args, cfg, encoder, eval_train_loader, epoch, cuda=Tr
                     cfg.DATASET.POSITIVE_SAMPLING_P = float(1.0 - NMI)
             except ImportError:
                 pass
+        if want_silhouette:
+            _silhouette_lines(cfg, epoch, embeddings, cluster_labels, silhouette_kernels)
         # one label per line, unshuffled dataset order (online_train.py:654-657); a slot the loader never produced is
         # written as the reference writes it ('None'), a DBSCAN noise row as its label, -1
         produced = np.zeros(n_data, dtype=bool)
