@@ -1,7 +1,7 @@
 """host-side launch planning of the gather-GEMM (no GPU needed)"""
 import os
 
-from video_similarity_search_amd.models.conv_plan import ConvPlan
+from video_similarity_search_amd.models.conv_plan import ConvPlan, LinearPlan
 from video_similarity_search_amd._lib import SlicConvArgs
 
 
@@ -102,3 +102,12 @@ def test_winograd_2d_plan_rules(monkeypatch):
         assert not pl.wino and not pl.wino2 and pl.wino_wgrad
     # non-uniform blocks (odd height whose tiles per frame do not divide 64): not eligible
     assert not ConvPlan(64, 64, k3, s1, p1, (4, 9, 20), "cpu", batch=64).wino2
+
+
+def test_linear_plan_is_the_1x1x1_conv_plan():
+    """LinearPlan(C, N) plans what ConvPlan plans for a 1x1x1 / stride 1 / no padding convolution of a single position, and is one"""
+    lp = LinearPlan(64, 32, "cpu")
+    cp = ConvPlan(64, 32, (1, 1, 1), (1, 1, 1), (0, 0, 0), (1, 1, 1), "cpu")
+    assert isinstance(lp, ConvPlan)
+    for a in ("N", "Cs", "Kp", "Kd", "ntaps", "out_dims", "wino", "wrun"):
+        assert getattr(lp, a) == getattr(cp, a), a

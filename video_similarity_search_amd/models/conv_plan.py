@@ -788,3 +788,35 @@ class ConvPlan:
         ws = _lib.workspace(lib.slic_conv_wgrad_workspace_bytes(ctypes.byref(a), splits), x.device, "wgrad")
         call("slic_conv_wgrad", ctypes.byref(a), ptr(dz), self.N, splits, self.C, self.ntaps, ptr(dW), ptr(ws), stream())
         return dW
+
+
+class LinearPlan(ConvPlan):
+    """A linear layer y = x W^T (+ b) on rows x [B, C] (C % 4 == 0): the 1x1x1 convolution of a [B, 1, 1, 1, C] tensor, so the engine's
+    _conv_bn_act and prepack() take it as any other plan.  The one place that writes the 5-D views, the weight / bias / data gradient
+    launches and slic_colsum.  What stays with each caller — when a pack is dropped or forced fresh, where a gradient lands, which
+    gradients are wanted — is tabulated in DESIGN.md §3 (linear layers).  Reads no requires_grad: callers hand over detached weights."""
+
+    def __init__(self, C, N, device):
+        super().__init__(C, N, (1, 1, 1), (1, 1, 1), (0, 0, 0), (1, 1, 1), device)
+
+    def rows_forward(self, x, weight, bias=None, relu=False, fresh=False):
+        """x [B, C] contiguous fp32 -> y [B, N]"""
+        B = x.shape[0]
+        return self.forward(x.view(B, 1, 1, 1, self.Cs), self.pack_fwd(weight, fresh=fresh), B, bias=bias, relu=relu)[0].view(B, self.N)
+
+    def rows_backward(self, x, dy, weight, *, need_dx, need_dw, need_db, mask=None, fresh=False, dW_out=None, db_out=None):
+        """x [B, C], dy [B, N] contiguous -> (dx [B, C], dW, db), None for what was not asked for; launches only what is asked for, in
+        this order.  dW_out / db_out: where to write (else new tensors).  mask [B, C]: dx = where(mask > 0, dx, 0), the ReLU that
+        produced x undone inside the data gradient"""
+        B = dy.shape[0]
+        dy5 = dy.view(B, 1, 1, 1, self.N)
+        dx = dW = db = None
+        if need_dw:
+            dW = self.wgrad(x.view(B, 1, 1, 1, self.Cs), dy5, B, torch.empty_like(weight) if dW_out is None else dW_out)
+        if need_db:
+            db = torch.empty(self.N, dtype=torch.float32, device=dy.device) if db_out is None else db_out
+            call("slic_colsum", ptr(dy), B, self.N, ptr(db), stream())
+        if need_dx:
+            dx = self.dgrad(dy5, self.pack_dgrad(weight, fresh=fresh), B,
+                            mask=None if mask is None else mask.view(B, 1, 1, 1, self.Cs)).view(B, self.Cs)
+        return dx, dW, db

@@ -14,8 +14,8 @@ What differs from the reference:
     callable returning a trunk module that maps a clip to pooled features [B, F] (F: its `feature_size` or `in_planes` attribute).
     The reference's only value, 's3d', raises NotImplementedError (the S3D backbone is not ported).
   * The Sequential is a parameter container.  The trunk runs through its own engine and returns pooled features; the head
-    (Conv3d 1x1x1 + bias, ReLU, Conv3d 1x1x1 + bias, F.normalize(dim=1, eps=1e-12)) is ONE autograd node on the linear kernels of
-    ConvPlan, slic_colsum and slic_l2normalize_fwd / _bwd.
+    (Conv3d 1x1x1 + bias, ReLU, Conv3d 1x1x1 + bias, F.normalize(dim=1, eps=1e-12)) is ONE autograd node on two LinearPlan layers
+    and slic_l2normalize_fwd / _bwd.
   * `queue` is the transposed view of a contiguous [K, dim] storage: the moco kernels read the rows in place, and an enqueue writes
     whole rows.
   * contrast(block, k_label=None, topk=(1, 5)) -> (loss, [acc_k ...]) is the same training step without the [B, 1 + K] matrix:
@@ -114,13 +114,13 @@ class HipInfoNCEKernels(HipMoCoKernels):
 
     # -- projection head
     def _plan(self, C, N, device):
-        from .conv_plan import ConvPlan
+        from .conv_plan import LinearPlan
         key = (C, N, str(device))
         plan = self._plans.get(key)
         if plan is None:
             if C % 4 or N % 4:
                 raise ValueError(f"InfoNCE head: feature size {C} and dim {N} must be multiples of 4")
-            plan = self._plans[key] = ConvPlan(C, N, (1, 1, 1), (1, 1, 1), (0, 0, 0), (1, 1, 1), device)
+            plan = self._plans[key] = LinearPlan(C, N, device)
         return plan
 
     def head_fwd(self, feat, w1, b1, w2, b2):
@@ -131,12 +131,12 @@ class HipInfoNCEKernels(HipMoCoKernels):
         p1.drop_packs()
         p2.drop_packs()
         feat = feat.contiguous().float()
-        h, _ = p1.forward(feat.view(B, 1, 1, 1, F), p1.pack_fwd(w1), B, bias=b1, relu=True)
-        z, _ = p2.forward(h, p2.pack_fwd(w2), B, bias=b2)
+        h = p1.rows_forward(feat, w1, bias=b1, relu=True)
+        z = p2.rows_forward(h, w2, bias=b2)
         y = torch.empty(B, N, dtype=torch.float32, device=feat.device)
         inv = torch.empty(B, dtype=torch.float32, device=feat.device)
         call("slic_l2normalize_fwd", ptr(z), B, N, NORMALIZE_EPS, ptr(y), ptr(inv), stream())
-        return y, (feat, h.view(B, F), inv)
+        return y, (feat, h, inv)
 
     def head_bwd(self, dy, y, saved, w1, w2, need_dx):
         """-> (d feat or None, dW1, db1, dW2, db2)"""
@@ -145,20 +145,15 @@ class HipInfoNCEKernels(HipMoCoKernels):
         p1, p2 = self._plan(F, F, feat.device), self._plan(F, N, feat.device)
         dz = torch.empty_like(y)
         call("slic_l2normalize_bwd", ptr(dy.contiguous().float()), ptr(y), ptr(inv), B, N, ptr(dz), stream())
-        dz5 = dz.view(B, 1, 1, 1, N)
-        gw2, gb2 = torch.empty_like(w2), torch.empty(N, dtype=torch.float32, device=dz.device)
-        p2.wgrad(h.view(B, 1, 1, 1, F), dz5, B, gw2)
-        call("slic_colsum", ptr(dz), B, N, ptr(gb2), stream())
-        dh = p2.dgrad(dz5, p2.pack_dgrad(w2), B, mask=h.view(B, 1, 1, 1, F))            # the ReLU's backward rides in the data gradient
-        gw1, gb1 = torch.empty_like(w1), torch.empty(F, dtype=torch.float32, device=dz.device)
-        p1.wgrad(feat.view(B, 1, 1, 1, F), dh, B, gw1)
-        call("slic_colsum", ptr(dh), B, F, ptr(gb1), stream())
-        dfeat = p1.dgrad(dh, p1.pack_dgrad(w1), B).view(B, F) if need_dx else None
+        # packs cached from head_fwd; the ReLU's backward rides in the second layer's data gradient (mask=h)
+        dh, gw2, gb2 = p2.rows_backward(h, dz, w2, need_dx=True, need_dw=True, need_db=True, mask=h)
+        dfeat, gw1, gb1 = p1.rows_backward(feat, dh, w1, need_dx=need_dx, need_dw=True, need_db=True)
         return dfeat, gw1, gb1, gw2, gb2
 
 
 class _Head(torch.autograd.Function):
-    """Conv3d 1x1x1 + bias -> ReLU -> Conv3d 1x1x1 + bias -> F.normalize(dim=1) on pooled features, as one node"""
+    """Conv3d 1x1x1 + bias -> ReLU -> Conv3d 1x1x1 + bias -> F.normalize(dim=1) on pooled features, as one node: two LinearPlan layers
+    (HipInfoNCEKernels.head_fwd / head_bwd; DESIGN.md §3, linear layers)"""
 
     @staticmethod
     def forward(ctx, feat, w1, b1, w2, b2, kern, keep):

@@ -14,8 +14,7 @@ import torch.nn as nn
 from torch.nn.modules.utils import _triple
 
 from .. import _lib
-from .._lib import call, ptr, stream
-from .conv_plan import ConvPlan
+from .conv_plan import LinearPlan
 from .resnet import _Engine, _flush_engine_counters, run_engine
 
 
@@ -139,35 +138,23 @@ class R3DNet(nn.Module):
 
 
 class _LinearFn(torch.autograd.Function):
-    """y = x W^T + b on the library's GEMM (slic_conv_gemm: a 1x1x1 convolution on a [B, 1, 1, 1, C] tensor — the route of the ResNet
-    head's fc1 / fc2, models/resnet.py), with its data / weight / bias gradients (slic_conv_gemm on the transposed operand, slic_conv_wgrad,
-    slic_colsum)."""
+    """y = x W^T + b and its data / weight / bias gradients on the module's LinearPlan (the route of the ResNet head's fc1 / fc2), both
+    packs forced fresh: nothing tells the plan when an optimizer has written the weights (linear layers)."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, mod):
-        B = x.shape[0]
-        plan = mod._plan(x.device)
         xc = x.contiguous()
-        y, _ = plan.forward(xc.view(B, 1, 1, 1, -1), plan.pack_fwd(weight, fresh=True), B, bias=bias)
+        y = mod._plan(x.device).rows_forward(xc, weight, bias=bias, fresh=True)
         ctx.save_for_backward(xc, weight)
         ctx.mod, ctx.has_bias = mod, bias is not None
-        return y.view(B, -1)
+        return y
 
     @staticmethod
     def backward(ctx, dy):
         x, weight = ctx.saved_tensors
-        B = x.shape[0]
-        plan = ctx.mod._plan(x.device)
-        d5 = dy.contiguous().view(B, 1, 1, 1, -1)
-        dx = dW = db = None
-        if ctx.needs_input_grad[0]:
-            dx = plan.dgrad(d5, plan.pack_dgrad(weight, fresh=True), B).view(B, -1)
-        if ctx.needs_input_grad[1]:
-            dW = plan.wgrad(x.view(B, 1, 1, 1, -1), d5, B, torch.empty_like(weight))
-        if ctx.has_bias and ctx.needs_input_grad[2]:
-            db = torch.empty(weight.shape[0], dtype=torch.float32, device=x.device)
-            call("slic_colsum", ptr(d5), B, weight.shape[0], ptr(db), stream())
-        return dx, dW, db, None
+        need_dx, need_dw, need_db = ctx.needs_input_grad[:3]
+        return ctx.mod._plan(x.device).rows_backward(x, dy.contiguous(), weight, need_dx=need_dx, need_dw=need_dw,
+                                                     need_db=ctx.has_bias and need_db, fresh=True) + (None,)
 
 
 class HipLinear(nn.Linear):
@@ -188,7 +175,7 @@ class HipLinear(nn.Linear):
         key = str(device)
         plan = self._plans.get(key)
         if plan is None:
-            plan = self._plans[key] = ConvPlan(self.in_features, self.out_features, (1, 1, 1), (1, 1, 1), (0, 0, 0), (1, 1, 1), device)
+            plan = self._plans[key] = LinearPlan(self.in_features, self.out_features, device)
         return plan
 
     def forward(self, x):

@@ -24,7 +24,7 @@ from functools import partial
 
 from .. import _lib
 from .._lib import call, ptr, stream
-from .conv_plan import COUNTS, ConvPlan
+from .conv_plan import COUNTS, ConvPlan, LinearPlan
 from .dropout import apply_mask, next_seed_offset
 
 BN_EPS = 1e-5
@@ -124,13 +124,6 @@ def _grad_out(p):
     return torch.empty_like(p, memory_format=torch.contiguous_format)
 
 
-def _bias_grad(d2, p):
-    """gradient of the bias p of a linear layer whose output gradient is d2 [B, features]: its column sums"""
-    g = _grad_out(p)
-    call("slic_colsum", ptr(d2), d2.shape[0], d2.shape[1], ptr(g), stream())
-    return g
-
-
 class _WgradStream:
     """the weight gradients of one seg_backward call: on `side` when there is one (beside the main stream's work), else on main"""
     def __init__(self, main, side, B):
@@ -212,16 +205,16 @@ class _Engine:
         self._prefused = {}    # (pass, si) -> (data_ptr, shape, partial sums) of a gradient whose ReLU mask + BN sums are done
         self.feat = self.p3.get(self.blocks[-1][0], self.blocks[-1][2]).N
         if net.projection_head:
-            self.fc1 = ConvPlan(net.fc1.in_features, net.fc1.out_features, (1, 1, 1), (1, 1, 1), (0, 0, 0), (1, 1, 1), device)
-            self.fc2 = ConvPlan(net.fc2.in_features, net.fc2.out_features, (1, 1, 1), (1, 1, 1), (0, 0, 0), (1, 1, 1), device)
+            self.fc1 = LinearPlan(net.fc1.in_features, net.fc1.out_features, device)
+            self.fc2 = LinearPlan(net.fc2.in_features, net.fc2.out_features, device)
         if net.classifier:
-            # `linear` as a 1x1x1 GEMM plan like fc1 / fc2.  The plan wants output channels in fours and num_classes is anything
+            # `linear` as a LinearPlan like fc1 / fc2.  The plan wants output channels in fours and num_classes is anything
             # (101, 51, 400): weight and bias are copied into zero-padded operands, the logits come back as the [B, num_classes]
             # view (row stride n_pad) of the padded product, and the padded columns of the gradient are zero
             lin = self.linear_mod
             self.n_cls = lin.out_features
             self.n_pad = (self.n_cls + 3) // 4 * 4
-            self.lin = ConvPlan(lin.in_features, self.n_pad, (1, 1, 1), (1, 1, 1), (0, 0, 0), (1, 1, 1), device)
+            self.lin = LinearPlan(lin.in_features, self.n_pad, device)
             self._lin_w = self._lin_b = None
 
     # ------------------------------------------------------------------ classifier head
@@ -250,7 +243,7 @@ class _Engine:
 
     def _classify(self, pooled, training, ctx):
         """pooled [B, 512] -> dropout (the Dropout child's own training flag, as in the reference) -> linear; ctx (or None) gets
-        what the backward needs"""
+        what the backward needs.  The linear layer is a LinearPlan whose forward pack is dropped first (linear layers)"""
         net = self.net
         B = pooled.shape[0]
         if net.projection_head and training:
@@ -268,42 +261,30 @@ class _Engine:
                 ctx["drop"] = key
         w, b = self._lin_operands()
         self.lin.drop_packs()
-        y, _ = self.lin.forward(xin.view(B, 1, 1, 1, self.feat), self.lin.pack_fwd(w), B, bias=b)
+        y = self.lin.rows_forward(xin, w, bias=b)
         if ctx is not None:
             ctx.update(xin=xin, lin_w=w)
-        y = y.view(B, self.n_pad)
         return y if self.n_pad == self.n_cls else y[:, :self.n_cls]
 
     def _classify_bwd(self, ctx, dy, need_dx):
         """returns (gradient wrt the pooled features or None, {parameter: gradient})"""
         lin = self.linear_mod
         B = dy.shape[0]
-        if self.n_pad != self.n_cls:
+        padded = self.n_pad != self.n_cls
+        if padded:
             dpad = torch.zeros(B, self.n_pad, dtype=torch.float32, device=dy.device)
             dpad[:, :self.n_cls].copy_(dy)
             dy = dpad
-        d5 = dy.view(B, 1, 1, 1, self.n_pad)
-        grads = {}
-        if lin.weight.requires_grad:               # a frozen weight launches no weight gradient
-            gw = _grad_out(lin.weight)
-            if self.n_pad == self.n_cls:
-                self.lin.wgrad(ctx["xin"].view(B, 1, 1, 1, self.feat), d5, B, gw)
-            else:
-                gwp = torch.empty(self.n_pad, lin.in_features, dtype=torch.float32, device=dy.device)
-                self.lin.wgrad(ctx["xin"].view(B, 1, 1, 1, self.feat), d5, B, gwp)
-                gw.copy_(gwp[:self.n_cls])
-            grads[lin.weight] = gw
-        if lin.bias.requires_grad and self.n_pad == self.n_cls:
-            grads[lin.bias] = _bias_grad(dy, lin.bias)
-        elif lin.bias.requires_grad:
-            gb = grads[lin.bias] = _grad_out(lin.bias)
-            gbp = torch.empty(self.n_pad, dtype=torch.float32, device=dy.device)
-            call("slic_colsum", ptr(dy), B, self.n_pad, ptr(gbp), stream())
+        # a frozen parameter launches no gradient; padded: the plan writes [n_pad, ...] temporaries, whose first n_cls rows are the gradients
+        grads = {p: _grad_out(p) for p in (lin.weight, lin.bias) if p.requires_grad}
+        gw, gb = grads.get(lin.weight), grads.get(lin.bias)
+        dpool, gwp, gbp = self.lin.rows_backward(ctx["xin"], dy, ctx["lin_w"], need_dx=need_dx, need_dw=gw is not None, need_db=gb is not None,
+                                                 dW_out=None if padded else gw, db_out=None if padded else gb)
+        if padded and gw is not None:
+            gw.copy_(gwp[:self.n_cls])
+        if padded and gb is not None:
             gb.copy_(gbp[:self.n_cls])
-        if not need_dx:
-            return None, grads
-        dpool = self.lin.dgrad(d5, self.lin.pack_dgrad(ctx["lin_w"]), B).view(B, self.feat)
-        if "drop" in ctx:
+        if need_dx and "drop" in ctx:
             dpool = apply_mask(dpool, *ctx["drop"], backward=True)
         return dpool, grads
 
@@ -592,11 +573,10 @@ class _Engine:
             return pooled, ctx
         h1, ah, bnp = self._conv_bn_act(self.fc1, pooled.view(B, 1, 1, 1, self.feat), net.fc1.weight, net.bn_proj, None, True, training, B,
                                         keep=save, bias=net.fc1.bias)
-        w2 = self.fc2.pack_fwd(net.fc2.weight)
-        y, _ = self.fc2.forward(ah.view(B, 1, 1, 1, -1), w2, B, bias=net.fc2.bias)
+        y = self.fc2.rows_forward(ah.view(B, -1), net.fc2.weight, bias=net.fc2.bias)
         if save:
             ctx.update(h1=h1, ah=ah, bnp=bnp)
-        return y.view(B, -1), ctx
+        return y, ctx
 
     def _live_ctx(self, pid, si):
         ref = self._live.get((pid, si))
@@ -626,6 +606,15 @@ class _Engine:
         wg.join()
         return res
 
+    @staticmethod
+    def _linear_bwd(plan, mod, x, dy, grads):
+        """backward of the projection head's nn.Linear `mod` on its LinearPlan (packs cached: prepack made them): the gradients of the
+        parameters that require one go to _grad_out and into `grads`; returns the data gradient"""
+        out = {p: _grad_out(p) for p in (mod.weight, mod.bias) if p.requires_grad}
+        grads.update(out)
+        gw, gb = out.get(mod.weight), out.get(mod.bias)
+        return plan.rows_backward(x, dy, mod.weight, need_dx=True, need_dw=gw is not None, need_db=gb is not None, dW_out=gw, db_out=gb)[0]
+
     def _head_backward(self, ctx, dy):
         net = self.net
         grads = {}
@@ -637,19 +626,10 @@ class _Engine:
                 return None, grads
         elif net.projection_head:
             ah, h1, bnp, pooled = ctx["ah"], ctx["h1"], ctx["bnp"], ctx["pooled"]
-            d5 = dy.view(B, 1, 1, 1, -1)
-            if net.fc2.weight.requires_grad:
-                grads[net.fc2.weight] = self.fc2.wgrad(ah.view(B, 1, 1, 1, -1), d5, B, _grad_out(net.fc2.weight))
-            if net.fc2.bias.requires_grad:
-                grads[net.fc2.bias] = _bias_grad(dy, net.fc2.bias)
-            dah = self.fc2.dgrad(d5, self.fc2.pack_dgrad(net.fc2.weight), B)
-            dh1, _, dg, db = self._bn_bwd(dah.view(B, -1), ah.view(B, -1), h1.view(B, -1), bnp, False)
+            dah = self._linear_bwd(self.fc2, net.fc2, ah.view(B, -1), dy, grads)
+            dh1, _, dg, db = self._bn_bwd(dah, ah.view(B, -1), h1.view(B, -1), bnp, False)
             grads[net.bn_proj.weight], grads[net.bn_proj.bias] = dg, db
-            if net.fc1.weight.requires_grad:
-                grads[net.fc1.weight] = self.fc1.wgrad(pooled.view(B, 1, 1, 1, -1), dh1.view(B, 1, 1, 1, -1), B, _grad_out(net.fc1.weight))
-            if net.fc1.bias.requires_grad:
-                grads[net.fc1.bias] = _bias_grad(dh1.view(B, -1), net.fc1.bias)
-            dpool = self.fc1.dgrad(dh1.view(B, 1, 1, 1, -1), self.fc1.pack_dgrad(net.fc1.weight), B).view(B, -1)
+            dpool = self._linear_bwd(self.fc1, net.fc1, pooled, dh1, grads)
         else:
             dpool = dy
         To, Ho, Wo = self.final_dims
