@@ -691,6 +691,52 @@ int slic_dbscan_cosine(const float* X, int64_t N, int ldx, int D, double eps, in
 int slic_dbscan_cosine_stats(const void* workspace, double* out_host /* [10] */, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * OPTICS, cosine metric, cluster_method='dbscan' (clustering/cluster_masks.py:88-89 -> sklearn.cluster.OPTICS(min_samples, max_eps,
+ * metric='cosine', cluster_method='dbscan', eps=None)): labels_, core_distances_, reachability_, predecessor_ and ordering_ of sklearn
+ * 1.7 (sklearn/cluster/_optics.py: compute_optics_graph, _set_reach_dist, cluster_optics_dbscan).  Rules:
+ *   1. Neighbour relation.  j is in N(i) iff d64(i, j) <= max_eps: exactly slic_dbscan_cosine's rule 1 (an fp32 score, a float64 recheck
+ *      from the raw rows inside a proven band around 1 - max_eps; d(i, i) = 0; a zero row is at distance 1 from every other row).  The
+ *      relation is symmetric and the same in every pass, the walk included.
+ *   2. Core rows.  i is core iff |N(i)| >= min_samples, the row itself counted.
+ *   3. Core distances.  d32(i, j) is ONE device function of the normalised zero-padded rows Xn_i, Xn_j: clip(1 - dot, 0, 2), the fp32
+ *      dot summed in a fixed order (lane l of a wave takes elements l, l + 64, ... by fmaf, then an xor butterfly), symmetric in its
+ *      arguments, d32(i, i) = 0.  core_distances_[i] = the min_samples-th smallest of {0} u {d32(i, j), j != i} for a core row, +inf
+ *      for a non-core row.  It is evaluated as d32(i, j_k), j_k the last entry of slic_cosine_topk's self-masked list of
+ *      min_samples - 1 rows for row i on Xn, so that the relax step below gets max(d32(p, j_k), cd[p]) == cd[p] bit for bit: the
+ *      structural ties of OPTICS are exact ties.  The core flag is decided in float64 and the value is fp32: a core row's value may
+ *      exceed max_eps by an fp32 rounding, where sklearn would write inf.
+ *   4. Walk.  reachability_ = +inf, predecessor_ = -1.  N times: take the unprocessed row p with the smallest reachability (an exact
+ *      tie goes to the lowest row index; when all are +inf that is the lowest unprocessed row) and append it to ordering_; if p is
+ *      core, every unprocessed j in N(p) gets r = max(d32(p, j), cd[p]) and, if r < reachability_[j] (strict), reachability_[j] = r,
+ *      predecessor_[j] = p.  (sklearn rounds r to 15 decimals in float64: nothing to reproduce in fp32.)
+ *   5. Labels (eps = max_eps).  Clusters = the connected components of the core rows under rule 1, numbered 0, 1, ... by their
+ *      smallest row.  A non-core row b with a core neighbour looks at the clusters of those neighbours, takes the one whose smallest
+ *      core row s is smallest and keeps it only if s < b; otherwise, and without a core neighbour, it is noise, -1.  (DBSCAN's rule 4
+ *      has no s < b test: the walk reaches such a row as a start of its own before any core of its clusters.)  The labels come from
+ *      parallel passes, not from the walk; cutting the walk's reachability plot at max_eps gives the same labels.
+ *   6. All outputs are fixed by rules 1-5: two runs are bit-equal.
+ * The walk runs every cluster at once (a cluster's walk touches its own rows only; ordering_ interleaves the clusters' blocks and the
+ * noise rows by start time), so the dependent steps are the largest cluster's rows, not N.
+ * X: [N, D] fp32, row stride ldx >= D.  Outputs (device): labels int32 [N], is_core uint8 [N] (NULL: not returned), core_dist fp32 [N],
+ * reachability fp32 [N], predecessor int32 [N], ordering int32 [N], *n_clusters int32 (NULL: not returned).  reachability, predecessor
+ * and ordering are given together or all NULL: NULL skips the walk (labels only; core_dist may then be NULL too, which also skips the
+ * core-distance search).  With the walk the call synchronises the stream once (the cluster sizes size its launches).
+ * SLIC_EINVAL for min_samples < 2, min_samples > N, min_samples > 89 (the search's list length), max_eps < 0 or not finite, D outside
+ * [1, 512], N < 1 or rows beyond slic_dbscan_cosine's limits.  No N x N matrix and no neighbour lists are written; the workspace is
+ * O(N * Dp + N * min_samples) (the label passes' 2 N Dp floats, the search's lists). */
+size_t slic_optics_cosine_workspace_bytes(int64_t N, int D, int min_samples);       /* 0 for arguments slic_optics_cosine rejects */
+int slic_optics_cosine(const float* X, int64_t N, int ldx, int D, double max_eps, int min_samples, int32_t* labels, uint8_t* is_core,
+                       float* core_dist, float* reachability, int32_t* predecessor, int32_t* ordering, int32_t* n_clusters,
+                       void* workspace, void* stream);
+/* after a slic_optics_cosine call with this workspace (synchronises the stream): out_host[0] = pairs rechecked in float64 by the label
+ * passes, [1] by the walk, [2] core rows, [3] clusters, [4] rows of the largest cluster = the walk's dependent steps, [5] those
+ * steps again as the host counted them, [6] launches of the walk, [7] clusters walked by the host loop (more rows than one workgroup
+ * keeps in LDS; the rest are walked by one workgroup each), [8..13] ms of the label passes prep / count / compact / link / number /
+ * border, [14] ms of the core distances, [15] ms of the walk when SLIC_OPTICS_TIMING=1 was set at the call (else -1; [3..7] are -1 / 0
+ * and [14], [15] -1 for the parts a labels-only call skipped).  Measurement only. */
+int slic_optics_cosine_stats(const void* workspace, double* out_host /* [16] */, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Average-linkage agglomerative clustering, cosine metric, cut by a distance threshold (clustering/cluster_masks.py:49-54 ->
  * sklearn.cluster.AgglomerativeClustering(n_clusters=None, linkage='average', distance_threshold=t, affinity='cosine')).
  * The rows are L2-normalised (slic_normalize_rows) and zero-padded to Dp = D rounded up to 8.  A cluster is the sum S of its unit rows and

@@ -158,6 +158,10 @@ SIGNATURES = {
     "slic_dbscan_cosine_workspace_bytes": (c_size_t, [L, I]),
     "slic_dbscan_cosine": (I, [P, L, I, I, Dbl, I, P, P, P, P, P, P]),
     "slic_dbscan_cosine_stats": (I, [P, P, P]),
+    # OPTICS (cosine, cluster_method='dbscan')
+    "slic_optics_cosine_workspace_bytes": (c_size_t, [L, I, I]),
+    "slic_optics_cosine": (I, [P, L, I, I, Dbl, I, P, P, P, P, P, P, P, P, P]),
+    "slic_optics_cosine_stats": (I, [P, P, P]),
     # average-linkage agglomerative clustering (cosine, distance threshold)
     "slic_agglo_workspace_bytes": (c_size_t, [L, I]),
     "slic_agglo_start": (I, [P, L, I, I, P, P, P]),

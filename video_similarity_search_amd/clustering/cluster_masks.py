@@ -5,8 +5,8 @@ Drop-in for the reference's clustering/cluster_masks.py on the k-means path:
 Same names, argument meaning, prints and return type (np.ndarray[N] labels).  method='kmeans'
 (SURVEY.md §8 A5/A6), method='finch' (§8f row 1: the method the shipped configs select) and
 method='DBSCAN' (cosine, clustering/dbscan.py) run on the GPU, and so does method='Agglomerative' (average linkage, cosine,
-clustering/agglomerative.py) once the caller states its distance_threshold; 'OPTICS', which the reference dispatches to sklearn
-on the host, raises.
+clustering/agglomerative.py) once the caller states its distance_threshold, and method='OPTICS' (cosine, cluster_method='dbscan',
+clustering/optics.py) once the caller states its max_eps.
 """
 import numpy as np
 import torch
@@ -44,7 +44,7 @@ def preprocess_features_kmeans(data, kernels=None):
 
 def fit_cluster(embeddings, method='Agglomerative', k=1000, l2normalize=True, finch_partition=0,
                 n_init=10, init='k-means++', process_group=None, random_state=None, kernels=None, exchange=None,
-                *, eps=0.14, min_samples=2, distance_threshold=None, precision=None):
+                *, eps=0.14, min_samples=None, distance_threshold=None, max_eps=None, precision=None):
     """Reference signature + keyword-only extras (n_init / init / process_group / random_state / kernels / exchange / eps /
     min_samples) that default to the reference's behaviour: KMeans(n_clusters=k, n_init=10).fit(embeddings).labels_, and for
     method='DBSCAN' DBSCAN(eps=0.14, min_samples=2, metric='cosine').fit(embeddings).labels_ (noise = -1; l2normalize does not
@@ -53,6 +53,10 @@ def fit_cluster(embeddings, method='Agglomerative', k=1000, l2normalize=True, fi
     distance_threshold=t, metric='cosine').fit(embeddings).labels_ (clustering/agglomerative.py: sklearn's partition, clusters numbered
     by their smallest row; `kernels` is then an agglomerative provider).  The reference's t is the hand-tuned constant 0.24 ("0.24 for
     ucf train", cluster_masks.py:52): the caller states it; without it the method raises NotImplementedError.
+    method='OPTICS' with max_eps=e runs OPTICS(min_samples=3, max_eps=e, cluster_method='dbscan', metric='cosine').fit(embeddings).labels_
+    (clustering/optics.py; `kernels` is then an OPTICS provider).  The reference's e is the hand-tuned 0.20 (cluster_masks.py:88-89, "0.18
+    for ucf val, 0.14 for ucf train, 0.12 for kin train"): the caller states it; without it the method raises NotImplementedError.
+    min_samples=None is the reference's own value for the method: 2 for 'DBSCAN', 3 for 'OPTICS'.
     process_group: `embeddings` is this rank's row shard (rank order == row order), the returned labels are this rank's.
     exchange: the sharded Lloyd iteration's one collective — 'allreduce' (RCCL through torch.distributed; the default), 'allgather', or
     'oneshot' (the library's one-shot all-to-all over peer-mapped memory, csrc/oneshot.hip); None reads SLIC_KMEANS_EXCHANGE.
@@ -75,7 +79,12 @@ def fit_cluster(embeddings, method='Agglomerative', k=1000, l2normalize=True, fi
     if method == 'DBSCAN':
         # cluster_masks.py:55-61: DBSCAN(eps=0.14, min_samples=2, metric='cosine', n_jobs=-1).fit(embeddings)
         from .dbscan import DBSCAN
-        km = DBSCAN(eps=eps, min_samples=min_samples, metric='cosine', kernels=kernels).fit(embeddings)
+        km = DBSCAN(eps=eps, min_samples=2 if min_samples is None else min_samples, metric='cosine', kernels=kernels).fit(embeddings)
+    elif method == 'OPTICS' and max_eps is not None:
+        # cluster_masks.py:88-89: OPTICS(min_samples=3, max_eps=0.20, cluster_method='dbscan', metric='cosine', n_jobs=-1).fit(embeddings)
+        from .optics import OPTICS
+        km = OPTICS(min_samples=3 if min_samples is None else min_samples, max_eps=max_eps, cluster_method='dbscan', metric='cosine',
+                    kernels=kernels).fit(embeddings)
     elif method == 'Agglomerative' and distance_threshold is not None:
         # cluster_masks.py:49-54: AgglomerativeClustering(n_clusters=None, linkage='average', distance_threshold=0.24, affinity='cosine')
         from .agglomerative import AgglomerativeClustering
@@ -84,8 +93,8 @@ def fit_cluster(embeddings, method='Agglomerative', k=1000, l2normalize=True, fi
     elif method not in ('kmeans', 'spherical_kmeans'):
         raise NotImplementedError(
             f"method={method!r}: 'kmeans', 'spherical_kmeans', 'finch' and 'DBSCAN' are on the MI355X hot path, and so is 'Agglomerative' "
-            "when the keyword distance_threshold= is given (the reference's hand-tuned 0.24 is not assumed); OPTICS is a sequential "
-            "algorithm the reference runs on the host through sklearn")
+            "when the keyword distance_threshold= is given (the reference's hand-tuned 0.24 is not assumed) and 'OPTICS' when the keyword "
+            "max_eps= is given (the reference's hand-tuned 0.20 is not assumed)")
     elif method == 'spherical_kmeans':
         x = _to_device(embeddings) if kernels is None else kernels.to_device(embeddings)
         # cluster_masks.py:73-77: SphericalKMeans(n_clusters=k).fit(embeddings) (spherecluster: normalises the rows itself,

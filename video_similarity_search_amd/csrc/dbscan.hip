@@ -21,17 +21,17 @@
 //   number  pointer jumping to the roots, a prefix scan over the root flags gives every root its cluster number.
 //   border  Xb x Xc (full rectangle): a hit takes atomicMin of the core's root; the smallest root is the smallest cluster number.
 // Every decision is an integer fixed by the float64 rule, so labels, core flags and counts are the same on every run.
+// csrc/optics.hip runs the same passes (db_label_passes, declared in dbscan_shared.h with the pieces the two files share) with one more
+// test in the border labelling.
 #include "mfma_ring.h"
+#include "dbscan_shared.h"
 #include <math.h>
 #include <limits.h>
 #include <stdlib.h>
 #include <algorithm>
 
-#define DB_B 128              // rows per tile (both operands)
 #define DB_PC 32              // band pairs pending per lane
 #define DB_SLICE 16           // gallery tiles per workgroup
-#define DB_SCAN_T 1024        // threads of the one-workgroup scans
-#define DB_NSTAT 8
 #define DB_SURE 0x40000000     // pending entry of the link pass that is a neighbour already (row indices < 2^30)
 
 enum { DB_COUNT = 0, DB_LINK = 1, DB_BORDER = 2 };
@@ -60,18 +60,6 @@ __device__ int db_unite(int* parent, int a, int b) {
     if (a > b) { const int t = a; a = b; b = t; }
     if (atomicCAS(parent + b, b, a) == b) return a;
   }
-}
-
-// the exact decision: float64 dot of the raw rows (lower index first, k ascending), times the float64 inverse norms
-__device__ bool db_exact(const float* __restrict__ X, int ldx, int D, const double* __restrict__ inv, int i, int j, double eps) {
-  const int a = min(i, j), b = max(i, j);
-  const float* xa = X + (int64_t)a * ldx;
-  const float* xb = X + (int64_t)b * ldx;
-  double s = 0.0;
-  for (int k = 0; k < D; ++k) s = fma((double)xa[k], (double)xb[k], s);
-  double d = 1.0 - s * inv[a] * inv[b];
-  d = fmin(fmax(d, 0.0), 2.0);
-  return d <= eps;
 }
 
 // prep: one wave per row
@@ -345,29 +333,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");             // the trailing all-zero DMAs must land before the workgroup leaves
 }
 
-// exclusive scan of one int per thread over a DB_SCAN_T-thread workgroup; returns the prefix, *total = the sum
-__device__ int db_block_scan(int v, int* sh, int* total) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  int x = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int y = __shfl_up(x, o);
-    if (lane >= o) x += y;
-  }
-  if (lane == 63) sh[w] = x;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int run = 0;
-    for (int i = 0; i < DB_SCAN_T / 64; ++i) { const int t = sh[i]; sh[i] = run; run += t; }
-    sh[DB_SCAN_T / 64] = run;
-  }
-  __syncthreads();
-  const int r = sh[w] + x - v;
-  *total = sh[DB_SCAN_T / 64];
-  __syncthreads();
-  return r;
-}
-
 // core flags, labels = -1, and the two compactions (core rows, border candidates) in row order
 __global__ __launch_bounds__(DB_SCAN_T) void db_compact(const int* __restrict__ cnt, int N, int min_samples,
                                                         uint8_t* __restrict__ is_core, int32_t* __restrict__ labels,
@@ -450,45 +415,20 @@ __global__ __launch_bounds__(256) void db_label_core(const int* __restrict__ par
   for (int c = blockIdx.x * blockDim.x + threadIdx.x; c < nc; c += gridDim.x * blockDim.x) labels[core_idx[c]] = cid[parent[c]];
 }
 
+// best[b] is the smallest root among the border row's core neighbours; a root is its component's smallest core, so cid[root] is the
+// smallest cluster number.  optics (slic_optics_cosine rule 5): the row keeps it only when that smallest core row is below the row itself.
 __global__ __launch_bounds__(256) void db_label_border(const int* __restrict__ best, const int* __restrict__ cid, const int* __restrict__ meta,
-                                                       const int* __restrict__ border_idx, int32_t* __restrict__ labels) {
+                                                       const int* __restrict__ core_idx, const int* __restrict__ border_idx, int optics,
+                                                       int32_t* __restrict__ labels) {
   const int nb = meta[2];
   for (int b = blockIdx.x * blockDim.x + threadIdx.x; b < nb; b += gridDim.x * blockDim.x) {
     const int r = best[b];
-    labels[border_idx[b]] = r == INT_MAX ? -1 : cid[r];
+    const int row = border_idx[b];
+    labels[row] = r == INT_MAX || (optics && core_idx[r] > row) ? -1 : cid[r];
   }
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------
-
-struct DbLayout {
-  unsigned long long* stats; int* meta; double* inv; float* Xn; float* Xcb; int* cnt;
-  int* core_idx; int* border_idx; int* parent; int* cid; int* best;
-};
-
-static size_t db_layout(void* base, int64_t N, int Dp, DbLayout* L) {
-  SlicCarver c(base);
-  DbLayout l;
-  l.stats = c.take<unsigned long long>(DB_NSTAT);             // first: slic_dbscan_cosine_stats reads it at the workspace's start
-  l.meta = c.take<int>(8);
-  l.inv = c.take<double>(N);
-  l.Xn = c.take<float>((size_t)N * Dp);
-  l.Xcb = c.take<float>((size_t)N * Dp);
-  l.cnt = c.take<int>(N);
-  l.core_idx = c.take<int>(N);
-  l.border_idx = c.take<int>(N);
-  l.parent = c.take<int>(N);
-  l.cid = c.take<int>(N);
-  l.best = c.take<int>(N);
-  if (L) *L = l;
-  return c.off;
-}
-
-static bool db_size_ok(int64_t N, int D) {
-  if (N < 1 || D < 1 || D > 512 || N > (1 << 30) - DB_B) return false;
-  const int64_t Dp = (D + 7) / 8 * 8;
-  return slic_cdiv(N, DB_B) * DB_B * Dp * 4 < (int64_t)0xFFFFFF00u;     // one 32-bit buffer range holds the rows
-}
 
 extern "C" size_t slic_dbscan_cosine_workspace_bytes(int64_t N, int D) {
   if (!db_size_ok(N, D)) return 0;
@@ -496,13 +436,12 @@ extern "C" size_t slic_dbscan_cosine_workspace_bytes(int64_t N, int D) {
 }
 
 // per-pass timing for scripts/bench_dbscan.py (SLIC_DBSCAN_TIMING=1 when the call is made): events between the passes
-#define DB_NEV 7              // (slic_dbscan_cosine_stats: out_host[4 .. 9])
-static hipEvent_t db_ev[DB_NEV];
+static hipEvent_t db_ev[DB_NEV];      // (slic_dbscan_cosine_stats: out_host[4 .. 9])
 static bool db_ev_on = false;
 
-static int db_mark(hipStream_t st, int i) {
-  if (!db_ev_on) return SLIC_OK;
-  SLIC_HIP_CHECK(hipEventRecord(db_ev[i], st));
+static int db_mark(hipStream_t st, hipEvent_t* ev, int i) {
+  if (!ev) return SLIC_OK;
+  SLIC_HIP_CHECK(hipEventRecord(ev[i], st));
   return SLIC_OK;
 }
 
@@ -524,18 +463,22 @@ extern "C" int slic_dbscan_cosine(const float* X, int64_t N, int ldx, int D, dou
                (long long)N, D);
   SLIC_REQUIRE(ldx >= D, "slic_dbscan_cosine: ldx = %d < D = %d", ldx, D);
   SLIC_REQUIRE(X && labels && is_core && n_clusters && workspace, "slic_dbscan_cosine: NULL argument");
-  hipStream_t st = S_(stream);
-  const int n = (int)N;
-  const int Dp = (D + 7) / 8 * 8;
-  const int NK = (Dp + 127) / 128 * 4;
   DbLayout L;
-  db_layout(workspace, N, Dp, &L);
-  int* cnt = counts ? counts : L.cnt;
+  db_layout(workspace, N, (D + 7) / 8 * 8, &L);
   const char* tenv = getenv("SLIC_DBSCAN_TIMING");
   db_ev_on = tenv && tenv[0] == '1';
   if (db_ev_on)
     for (int i = 0; i < DB_NEV; ++i)
       if (!db_ev[i]) SLIC_HIP_CHECK(hipEventCreate(&db_ev[i]));
+  return db_label_passes(X, (int)N, ldx, D, eps, min_samples, labels, is_core, counts, n_clusters, L, false, db_ev_on ? db_ev : nullptr,
+                         S_(stream));
+}
+
+int db_label_passes(const float* X, int n, int ldx, int D, double eps, int min_samples, int32_t* labels, uint8_t* is_core, int32_t* counts,
+                    int32_t* n_clusters, const DbLayout& L, bool optics_border, hipEvent_t* ev, hipStream_t st) {
+  const int Dp = (D + 7) / 8 * 8;
+  const int NK = (Dp + 127) / 128 * 4;
+  int* cnt = counts ? counts : L.cnt;
 
   // screening band: |s_fp32 - s_fp64| <= (Dp + 2) u for unit rows, doubled for margin
   const double delta = 2.0 * (Dp + 4) * ldexp(1.0, -24);
@@ -553,10 +496,10 @@ extern "C" int slic_dbscan_cosine(const float* X, int64_t N, int ldx, int D, dou
   SLIC_HIP_CHECK(hipMemsetAsync(L.stats, 0, DB_NSTAT * sizeof(unsigned long long), st));
   SLIC_HIP_CHECK(hipMemcpyAsync(L.meta, &n, sizeof(int), hipMemcpyHostToDevice, st));
   SLIC_HIP_CHECK(hipMemsetAsync(cnt, 0, (size_t)n * sizeof(int), st));
-  { int r = db_mark(st, 0); if (r) return r; }
+  { int r = db_mark(st, ev, 0); if (r) return r; }
   db_prep<<<(n + 3) / 4, 256, 0, st>>>(X, n, ldx, D, Dp, L.inv, L.Xn);
   SLIC_LAUNCH_CHECK();
-  { int r = db_mark(st, 1); if (r) return r; }
+  { int r = db_mark(st, ev, 1); if (r) return r; }
 
   DbArgs a;
   a.Dp = Dp; a.meta = L.meta; a.hi = hi; a.lo = lo;
@@ -569,16 +512,16 @@ extern "C" int slic_dbscan_cosine(const float* X, int64_t N, int ldx, int D, dou
 
   a.Xcb = L.Xn;
   { int r = db_launch_tiles<DB_COUNT>(NK, grid, LDS, st, a); if (r) return r; }
-  { int r = db_mark(st, 2); if (r) return r; }
+  { int r = db_mark(st, ev, 2); if (r) return r; }
   db_compact<<<1, DB_SCAN_T, 0, st>>>(cnt, n, min_samples, is_core, labels, L.core_idx, L.border_idx, L.meta);
   SLIC_LAUNCH_CHECK();
   const int gb = (int)std::min<int64_t>(4096, slic_cdiv((int64_t)n * Dp / 4, 256));
   db_gather<<<gb, 256, 0, st>>>(L.Xn, n, Dp, L.meta, L.core_idx, L.border_idx, L.Xcb, L.parent, L.best);
   SLIC_LAUNCH_CHECK();
-  { int r = db_mark(st, 3); if (r) return r; }
+  { int r = db_mark(st, ev, 3); if (r) return r; }
   a.Xcb = L.Xcb;
   { int r = db_launch_tiles<DB_LINK>(NK, grid, LDS, st, a); if (r) return r; }
-  { int r = db_mark(st, 4); if (r) return r; }
+  { int r = db_mark(st, ev, 4); if (r) return r; }
   const int gn = (int)std::min<int64_t>(4096, slic_cdiv(n, 256));
   db_compress<<<gn, 256, 0, st>>>(L.parent, L.meta);
   SLIC_LAUNCH_CHECK();
@@ -586,12 +529,12 @@ extern "C" int slic_dbscan_cosine(const float* X, int64_t N, int ldx, int D, dou
   SLIC_LAUNCH_CHECK();
   db_label_core<<<gn, 256, 0, st>>>(L.parent, L.cid, L.meta, L.core_idx, labels);
   SLIC_LAUNCH_CHECK();
-  { int r = db_mark(st, 5); if (r) return r; }
+  { int r = db_mark(st, ev, 5); if (r) return r; }
   // border rows: only the candidates the compaction listed (none at min_samples <= 2: every workgroup leaves at once)
   { int r = db_launch_tiles<DB_BORDER>(NK, grid, LDS, st, a); if (r) return r; }
-  db_label_border<<<gn, 256, 0, st>>>(L.best, L.cid, L.meta, L.border_idx, labels);
+  db_label_border<<<gn, 256, 0, st>>>(L.best, L.cid, L.meta, L.core_idx, L.border_idx, optics_border ? 1 : 0, labels);
   SLIC_LAUNCH_CHECK();
-  { int r = db_mark(st, 6); if (r) return r; }
+  { int r = db_mark(st, ev, 6); if (r) return r; }
   return SLIC_OK;
 }
 
