@@ -5,6 +5,8 @@ import os
 
 import numpy as np
 
+from host_rows import host_rows
+
 
 def golden_cases():
     """(name, X, t, canonical labels) of every case of tests/golden/agglomerative.npz"""
@@ -32,16 +34,7 @@ class NumpyAggloKernels:
         self.heights = []
 
     def resident(self, data):
-        try:
-            import torch
-            if torch.is_tensor(data):
-                data = data.detach().cpu().numpy()
-        except ImportError:
-            pass
-        x = np.ascontiguousarray(np.asarray(data, dtype=np.float32))
-        if x.ndim != 2:
-            raise ValueError("AgglomerativeClustering expects a 2-D array")
-        return x
+        return host_rows(data, "AgglomerativeClustering")
 
     def start(self, rows):
         x = rows.astype(np.float64)

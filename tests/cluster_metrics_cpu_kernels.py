@@ -5,6 +5,8 @@ import math
 
 import numpy as np
 
+from host_rows import host_labels
+
 G, T = 1024, 256                     # CM_G workgroups x CM_T threads of every fixed-order sum
 MAX_CELLS = 1 << 26                  # SLIC_METRICS_MAX_CELLS
 EPS = float(np.finfo(np.float64).eps)
@@ -148,10 +150,7 @@ def cluster_metrics_fp64(labels_true, labels_pred):
 
 
 class NumpyClusterMetricsKernels:
-    def resident(self, labels):
-        if hasattr(labels, "detach"):
-            labels = labels.detach().cpu().numpy()
-        return np.ascontiguousarray(labels, dtype=np.int32)
+    resident = staticmethod(host_labels)
 
     def metrics(self, labels_true, labels_pred):
         return cluster_metrics_fp64(labels_true, labels_pred)

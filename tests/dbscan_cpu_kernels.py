@@ -5,6 +5,8 @@ import numpy as np
 from scipy.sparse import coo_matrix
 from scipy.sparse.csgraph import connected_components
 
+from host_rows import host_rows
+
 
 def inv_norms(X):
     """float64 1 / ||x|| of every row, 0 for a zero row"""
@@ -77,16 +79,7 @@ class NumpyDbscanKernels:
         self.last_stats = None
 
     def resident(self, data):
-        try:
-            import torch
-            if torch.is_tensor(data):
-                data = data.detach().cpu().numpy()
-        except ImportError:
-            pass
-        x = np.ascontiguousarray(np.asarray(data, dtype=np.float32))
-        if x.ndim != 2:
-            raise ValueError("DBSCAN expects a 2-D array")
-        return x
+        return host_rows(data, "DBSCAN")
 
     def dbscan(self, rows, eps, min_samples):
         return dbscan_fp64(rows, eps, min_samples)

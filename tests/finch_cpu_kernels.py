@@ -3,10 +3,12 @@ logic of clustering/finch.py (link list, weighted early-exit cut, hierarchy book
 against the reference goldens on a GPU-less machine.  Never shipped, never imported by the package."""
 import numpy as np
 
+from host_rows import host_rows
+
 
 class NumpyFinchKernels:
     def resident(self, mat):
-        return np.ascontiguousarray(np.asarray(mat, dtype=np.float32))
+        return host_rows(mat, "FINCH")
 
     @staticmethod
     def _unit(rows):

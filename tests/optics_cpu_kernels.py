@@ -6,6 +6,8 @@ import numpy as np
 from scipy.sparse import coo_matrix
 from scipy.sparse.csgraph import connected_components
 
+from host_rows import host_rows
+
 
 def fp64_distances(X):
     """rule 1's distance: float64 from the raw fp32 rows, d(i, i) = 0, a zero row at distance 1 from every other row"""
@@ -110,16 +112,7 @@ class NumpyOpticsKernels:
         self.last_stats = None
 
     def resident(self, data):
-        try:
-            import torch
-            if torch.is_tensor(data):
-                data = data.detach().cpu().numpy()
-        except ImportError:
-            pass
-        x = np.ascontiguousarray(np.asarray(data, dtype=np.float32))
-        if x.ndim != 2:
-            raise ValueError("OPTICS expects a 2-D array")
-        return x
+        return host_rows(data, "OPTICS")
 
     def optics(self, rows, max_eps, min_samples, walk=True):
         o = optics_fp64(rows, max_eps, min_samples)

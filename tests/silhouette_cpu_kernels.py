@@ -12,6 +12,8 @@
 """
 import numpy as np
 
+from host_rows import host_labels, host_rows
+
 DEFECTS = ("self_kept", "n_for_n_minus_1", "own_in_b", "singleton_kept", "ties_last")
 U = 2.0 ** -24
 F32, F64 = np.float32, np.float64
@@ -193,10 +195,9 @@ class NumpySilhouetteKernels:
 
     def resident_rows(self, X):
         assert not (hasattr(X, "is_cuda") and X.is_cuda)
-        return np.ascontiguousarray(X, dtype=np.float32)
+        return host_rows(X, "the silhouette")
 
-    def resident_labels(self, labels):
-        return np.ascontiguousarray(labels, dtype=np.int32)
+    resident_labels = staticmethod(host_labels)
 
     def take(self, x, idx):
         return x[np.asarray(idx, np.int64)]

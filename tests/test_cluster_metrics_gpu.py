@@ -60,6 +60,22 @@ def test_working_sizes_against_the_provider(gpu, which):
     assert np.abs(got - ref[:6]).max() <= GATE, (got, ref)
 
 
+@pytest.mark.parametrize("N", [1, 2, 4095, 4096, 4097, 1023, 1024, 1025])
+def test_scan_sizes_against_the_provider(gpu, N):
+    """the one-workgroup array scan (1024 threads, runs of ceil(n / 1024) elements) on either side of 1024 elements: the radix histogram
+    holds 16 * ceil(N / 64) counters (1024 at N = 4096), the head flags N"""
+    rng = np.random.default_rng(1000 + N)
+    lt = rng.integers(-3, 9, N).astype(np.int32)
+    lp = np.where(rng.random(N) < 0.5, lt * 3 + rng.integers(0, 3, N), rng.integers(-40, 40, N)).astype(np.int32)
+    s = _scores(torch.from_numpy(lt).cuda(), torch.from_numpy(lp).cuda())
+    ref = cluster_metrics_fp64(lt, lp)
+    got = np.array([s[k] for k in KEYS])
+    print("N", N, "max |device - provider| =", np.abs(got - ref[:6]).max())
+    assert (s["n_classes"], s["n_clusters"]) == (int(ref[6]), int(ref[7])) and ref[8] == 0
+    assert (s["n_classes"], s["n_clusters"]) == (len(np.unique(lt)), len(np.unique(lp)))
+    assert np.abs(got - ref[:6]).max() <= GATE, (got, ref)
+
+
 def test_bit_identical_across_runs_and_input_forms(gpu):
     lt, lp = working_size(1)
     lt, lp = lt[:30000], lp[:30000] - 7000                                        # negative values too

@@ -59,6 +59,22 @@ def test_matches_fp64_oracle(gpu, N, D, eps, ms):
     assert m.n_clusters_ > 1 and (m.labels_ == -1).any()
 
 
+# N -> seed of _blobs: N + 8 where the float64 oracle alone then has core rows, border candidates and noise rows, else the next that has
+SCAN_SEEDS = {1: 9, 2: 10, 63: 71, 64: 73, 65: 74, 1023: 1032, 1024: 1032, 1025: 1033, 2049: 2057}
+
+
+@pytest.mark.parametrize("N", sorted(SCAN_SEEDS))
+def test_matches_fp64_oracle_at_the_scan_sizes(gpu, N):
+    """the one-workgroup scans of db_compact and db_number (1024 threads, runs of ceil(N / 1024) rows): a partly filled last wave, empty
+    trailing runs, runs of 1 next to runs of 2; all three outputs of the compaction non-empty from N = 63 on"""
+    D, eps, ms = 8, 0.05, 3
+    X = _blobs(SCAN_SEEDS[N], N, D, K=max(4, N // 400), spread=0.15)
+    labels, core, counts, ncl = dbscan_fp64(X, eps, ms)
+    if N >= 63:
+        assert core.any() and ((counts >= 2) & ~core).any() and (labels == -1).any()
+    _check_against_oracle(X, eps, ms)
+
+
 def test_screening_band_decided_in_fp64(gpu):
     """chains of rows in disjoint 2-D planes: consecutive rows sit within 1e-7 of the eps boundary on either side (fp32 cannot
     tell), non-consecutive ones far away; counts, cores and labels must be the float64 decision's"""

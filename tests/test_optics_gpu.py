@@ -61,6 +61,52 @@ def test_g1_golden_exact_order(gpu, case):
     assert m.stats_["walk_steps"] == np.bincount(o["labels"][o["labels"] >= 0]).max() and m.stats_["host_loop_clusters"] == 0
 
 
+# ---------------------------------------------------------------------------------------------------------------- G1 at the scan's sizes
+
+SCAN_D, SCAN_EPS, SCAN_MS = 16, 0.05, 3
+# N -> seed: the first seed from N on whose float64 walk has gap >= 4 (Dp + 8) 2^-24 (the goldens' condition, asserted below) and,
+# from N = 63 on, noise rows, two or more clusters and a border row, so that op_offsets places blocks of 1, of a cluster's size and of 0 rows
+SCAN_SEEDS = {2: 2, 63: 65, 64: 88, 65: 71, 1023: 1043, 1024: 1025, 1025: 1058}
+
+
+def _groups(seed, N):
+    """N rows around far-apart centres: up to 12 groups of 3 .. 6 rows (clusters at min_samples = 3), the rest single rows and pairs (noise).
+    Few clusters, so that a seed exists at every N whose walk never compares two values an ulp apart."""
+    rng = np.random.default_rng(seed)
+    sizes = [int(s) for s in rng.integers(3, 7, min(12, N // 5))]
+    while sum(sizes) < N:
+        sizes.append(min(int(rng.integers(1, 3)), N - sum(sizes)))
+    cen = rng.standard_normal((len(sizes), SCAN_D))
+    X = np.repeat(cen, sizes, axis=0) + 0.1 * rng.uniform(0.5, 2.0, (N, 1)) * rng.standard_normal((N, SCAN_D))
+    return X[rng.permutation(N)].astype(np.float32)
+
+
+@pytest.mark.parametrize("N", [1, 2, 63, 64, 65, 1023, 1024, 1025])
+def test_g1_exact_order_at_the_scan_sizes(gpu, N):
+    """the one-workgroup scan of op_offsets (1024 threads, runs of ceil(N / 1024) rows) with a partly filled last wave, empty trailing runs
+    and runs of 1 next to runs of 2; G1's comparison against the float64 walk"""
+    from video_similarity_search_amd.clustering.optics import OPTICS
+    if N == 1:                                                                # min_samples <= N is a rule of the call: no launch
+        with pytest.raises(ValueError, match="no greater than the number of samples"):
+            OPTICS(min_samples=2, max_eps=SCAN_EPS).fit(torch.zeros(1, SCAN_D, device="cuda") + 1)
+        return
+    ms = min(SCAN_MS, N)
+    X = _groups(SCAN_SEEDS[N], N)
+    o = optics_fp64(X, SCAN_EPS, ms, want_gap=True)
+    tol = (_dp(X) + 8) * U
+    assert o["gap"] >= 4 * tol
+    if N >= 63:
+        assert (o["labels"] < 0).any() and o["n_clusters"] >= 2 and ((o["labels"] >= 0) & ~o["is_core"]).any()
+    m = OPTICS(min_samples=ms, max_eps=SCAN_EPS).fit(torch.from_numpy(X).cuda())
+    assert np.array_equal(m.labels_, o["labels"])
+    assert np.array_equal(np.isfinite(m.core_distances_), o["is_core"])
+    assert np.array_equal(m.ordering_, o["ordering"])
+    assert np.array_equal(m.predecessor_, o["predecessor"])
+    assert _close(m.reachability_, o["reachability"], tol)
+    assert _close(m.core_distances_, o["core_distances"], tol)
+    assert m.n_clusters_ == o["n_clusters"]
+
+
 # ---------------------------------------------------------------------------------------------------------------- G3 data
 
 def _scrub(X, max_eps, margin, fill):

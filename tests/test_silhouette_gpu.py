@@ -96,6 +96,17 @@ def test_edges(gpu, shape, metric):
     assert last.any() and np.array_equal(np.isnan(out["s"][last]), np.isnan(ref["s"][last]))
 
 
+@pytest.mark.parametrize("shape,metric", [((1025, 8, 12), "cosine"), ((4097, 8, 40), "sqeuclidean")], ids=["n1025", "n4097"])
+def test_label_scan_sizes(gpu, shape, metric):
+    """the dense ids' one-workgroup array scan past 1024 elements: the head flags (N = 1025), the radix histogram (16 * ceil(N / 64) = 1040
+    counters at N = 4097)"""
+    N, D, K = shape
+    x, labels = draw(1000 + N + D + K, N, D, K, 0.3, singletons=3)
+    ref = silhouette_fp64(x, labels, metric)
+    assert ref["n_clusters"] == K
+    check_against(raw_call(*dev(x, labels), metric), x, labels, metric, ref, "n{} d{} k{} {}".format(N, D, K, metric))
+
+
 @pytest.mark.parametrize("metric", METRICS)
 def test_one_large_cluster(gpu, metric):
     x, labels = draw(31, 517, 24, 9, 0.3, singletons=0)

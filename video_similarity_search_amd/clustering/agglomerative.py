@@ -30,6 +30,7 @@ import torch
 
 from .. import _lib
 from .._lib import call, ptr, stream
+from ._device import require_device, resident_rows, workspace_bytes
 
 
 class HipAggloKernels:
@@ -38,29 +39,18 @@ class HipAggloKernels:
     product has no other)."""
 
     def __init__(self):
-        _lib.load()
-        if not torch.cuda.is_available():
-            raise _lib.SlicError("AgglomerativeClustering needs a gfx950 device for its nearest-cluster search (no CPU fallback)")
+        require_device("AgglomerativeClustering")
 
     def resident(self, data):
         """fp32 device rows with unit column stride (no copy when they already are)"""
-        if torch.is_tensor(data):
-            x = data.detach().to(device="cuda", dtype=torch.float32)
-        else:
-            x = torch.as_tensor(np.ascontiguousarray(data, dtype=np.float32)).cuda()
-        if x.dim() != 2:
-            raise ValueError("AgglomerativeClustering expects a 2-D array [n_samples, n_features], got shape {}".format(tuple(x.shape)))
-        if x.stride(1) != 1 or x.stride(0) < x.shape[1]:
-            x = x.contiguous()
-        return x
+        return resident_rows(data, "AgglomerativeClustering")
 
     def start(self, rows):
         """every row a cluster of its own; -> the number of rows that cannot be normalised (zero norm or a non-finite value)"""
         N, D = rows.shape
         _lib.require_device(rows)
-        nbytes = _lib.load().slic_agglo_workspace_bytes(N, D)
-        if nbytes == 0:
-            raise _lib.SlicError("AgglomerativeClustering: {} x {} rows are outside what slic_agglo_start takes (1 <= D <= 512, "
+        nbytes = workspace_bytes("slic_agglo_workspace_bytes", (N, D),
+                                 "AgglomerativeClustering: {} x {} rows are outside what slic_agglo_start takes (1 <= D <= 512, "
                                  "N <= 2^24, < 4 GiB padded)".format(N, D))
         self.N, self.D, self.A, self.Q = N, D, N, N
         self.ws = torch.empty(nbytes, dtype=torch.uint8, device=rows.device)

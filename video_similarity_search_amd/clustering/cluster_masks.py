@@ -8,36 +8,29 @@ method='DBSCAN' (cosine, clustering/dbscan.py) run on the GPU, and so does metho
 clustering/agglomerative.py) once the caller states its distance_threshold, and method='OPTICS' (cosine, cluster_method='dbscan',
 clustering/optics.py) once the caller states its max_eps.
 """
-import numpy as np
 import torch
 
-from .. import _lib
-from .._lib import call, ptr, stream
-from .kmeans_hip import KMeans
+from ._device import require_device, resident_rows
+from .kmeans_hip import HipKernels, KMeans
 
 _METHODS = ['DBSCAN', 'Agglomerative', 'OPTICS', 'kmeans', 'spherical_kmeans', 'finch']
 
 
 def _to_device(embeddings):
-    if not torch.cuda.is_available():
-        raise _lib.SlicError("fit_cluster needs a gfx950 device (no CPU fallback)")
-    if not torch.is_tensor(embeddings):
-        embeddings = torch.as_tensor(np.ascontiguousarray(embeddings, dtype=np.float32))
-    return embeddings.detach().to(device="cuda", dtype=torch.float32).contiguous()
+    require_device("fit_cluster")
+    return resident_rows(embeddings, "fit_cluster", dense=True)
 
 
 def preprocess_features_kmeans(data, kernels=None):
     """row L2-normalise: data / torch.norm(data, dim=1, keepdim=True) (no epsilon), on the device.
     Returns a tensor on the device the data ended up on (CPU input is moved to the current GPU)."""
-    if kernels is not None:                 # explicit kernel provider (see KMeans(kernels=...)): tests of the host logic
-        x = kernels.to_device(data)
-        out = torch.empty_like(x)
-        kernels.l2norm_rows(x, out)
-    else:
+    if kernels is None:
+        kernels = HipKernels()
         x = _to_device(data)
-        out = torch.empty_like(x)
-        N, D = x.shape
-        call("slic_l2norm_rows", ptr(x), N, D, x.stride(0), ptr(out), out.stride(0), stream())
+    else:                                   # explicit kernel provider (see KMeans(kernels=...)): tests of the host logic
+        x = kernels.to_device(data)
+    out = torch.empty_like(x)
+    kernels.l2norm_rows(x, out)
     print('l2-normalized data')
     return out
 

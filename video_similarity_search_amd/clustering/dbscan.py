@@ -14,6 +14,10 @@ import torch
 
 from .. import _lib
 from .._lib import call, ptr, stream
+from ._device import require_device, resident_rows, sized_workspace
+
+_STATS = ("band_rechecks", "skipped_tiles", "core_rows", "border_candidates", "ms_prep", "ms_count", "ms_compact", "ms_link", "ms_number",
+          "ms_border")
 
 
 class HipDbscanKernels:
@@ -21,32 +25,20 @@ class HipDbscanKernels:
     same two methods (tests of the host logic on a GPU-less machine pass a NumPy one as an ARGUMENT; the product has no other)."""
 
     def __init__(self):
-        _lib.load()
-        if not torch.cuda.is_available():
-            raise _lib.SlicError("DBSCAN needs a gfx950 device for its neighbour search (no CPU fallback)")
+        require_device("DBSCAN")
         self.last_stats = None
 
     def resident(self, data):
         """fp32 device rows with unit column stride (no copy when they already are)"""
-        if torch.is_tensor(data):
-            x = data.detach().to(device="cuda", dtype=torch.float32)
-        else:
-            x = torch.as_tensor(np.ascontiguousarray(data, dtype=np.float32)).cuda()
-        if x.dim() != 2:
-            raise ValueError("DBSCAN expects a 2-D array [n_samples, n_features], got shape {}".format(tuple(x.shape)))
-        if x.stride(1) != 1 or x.stride(0) < x.shape[1]:
-            x = x.contiguous()
-        return x
+        return resident_rows(data, "DBSCAN")
 
     def dbscan(self, rows, eps, min_samples):
         """-> (labels int32 [N], is_core bool [N], counts int32 [N], n_clusters) as host arrays"""
         N, D = rows.shape
         _lib.require_device(rows)
-        nbytes = _lib.load().slic_dbscan_cosine_workspace_bytes(N, D)
-        if nbytes == 0:
-            raise _lib.SlicError("DBSCAN: {} x {} rows are outside what slic_dbscan_cosine takes (1 <= D <= 512, rows of "
-                                 "int32 indices, < 4 GiB padded)".format(N, D))
-        ws = _lib.workspace(nbytes, rows.device, tag="dbscan")
+        ws = sized_workspace("slic_dbscan_cosine_workspace_bytes", (N, D), rows.device, "dbscan",
+                             "DBSCAN: {} x {} rows are outside what slic_dbscan_cosine takes (1 <= D <= 512, rows of int32 indices, "
+                             "< 4 GiB padded)".format(N, D))
         labels = torch.empty(N, dtype=torch.int32, device=rows.device)
         core = torch.empty(N, dtype=torch.uint8, device=rows.device)
         counts = torch.empty(N, dtype=torch.int32, device=rows.device)
@@ -54,10 +46,9 @@ class HipDbscanKernels:
         call("slic_dbscan_cosine", ptr(rows), N, rows.stride(0), D, float(eps), int(min_samples), ptr(labels), ptr(core),
              ptr(counts), ptr(ncl), ptr(ws), stream())
         out = torch.cat([labels, core.to(torch.int32), counts, ncl]).cpu().numpy()
-        st = (ctypes.c_double * 10)()
+        st = (ctypes.c_double * len(_STATS))()
         call("slic_dbscan_cosine_stats", ptr(ws), st, stream())
-        self.last_stats = dict(zip(("band_rechecks", "skipped_tiles", "core_rows", "border_candidates", "ms_prep", "ms_count",
-                                    "ms_compact", "ms_link", "ms_number", "ms_border"), list(st)))
+        self.last_stats = dict(zip(_STATS, list(st)))
         return out[:N], out[N:2 * N].astype(bool), out[2 * N:3 * N], int(out[3 * N])
 
 

@@ -35,9 +35,9 @@ import scipy.sparse as sp
 from scipy.sparse.csgraph import connected_components
 import torch
 
-from .. import _lib
 from .._lib import call, ptr, stream
 from ..evaluate import cosine_topk
+from ._device import require_device, resident_rows
 from .kmeans_hip import HipKernels
 
 
@@ -47,16 +47,12 @@ class HipFinchKernels:
     four methods (tests of the host logic on a GPU-less machine pass a NumPy one as an ARGUMENT; the product has no other)."""
 
     def __init__(self):
-        _lib.load()
-        if not torch.cuda.is_available():
-            raise _lib.SlicError("FINCH needs a gfx950 device for its first-neighbour search (no CPU fallback)")
+        require_device("FINCH")
         self.kern = HipKernels()
 
     def resident(self, mat):
         """fp32 device copy of the rows (no copy when they already are one)"""
-        if torch.is_tensor(mat):
-            return mat.detach().to(device="cuda", dtype=torch.float32).contiguous()
-        return torch.as_tensor(np.ascontiguousarray(mat, dtype=np.float32)).cuda()
+        return resident_rows(mat, "FINCH", dense=True)
 
     def first_neighbours(self, rows):
         """index of the nearest OTHER row (cosine) for every row of a device matrix; a single row is its own neighbour"""

@@ -43,6 +43,7 @@ import torch
 
 from .. import _lib
 from .._lib import call, ptr, stream
+from ._device import require_device, resident_rows
 from .kmeans_exchange import Exchange, _slic_oneshot  # noqa: F401 — tests/dist_gpu_worker.py reaches the one-shot set-up through this module
 
 
@@ -67,14 +68,11 @@ class HipKernels:
     has_bf16 = True
 
     def check(self):
-        if not torch.cuda.is_available():
-            raise _lib.SlicError("k-means needs a gfx950 device: libslic_hip.so has no CPU path")
+        require_device("k-means")
         _lib.check(_lib.load().slic_device_check(), "slic_device_check")
 
     def to_device(self, X):
-        if not torch.is_tensor(X):
-            X = torch.as_tensor(np.ascontiguousarray(X, dtype=np.float32))
-        return X.detach().to(device="cuda", dtype=torch.float32).contiguous()
+        return resident_rows(X, "k-means", dense=True)
 
     def col_stats(self, X):
         N, Dp = X.shape

@@ -15,6 +15,7 @@ import torch
 
 from .. import _lib
 from .._lib import call, ptr, stream
+from ._device import require_device, resident_labels, resident_rows, sized_workspace
 
 MAX_N = 1 << 24             # SLIC_METRICS_MAX_N
 MAX_CELLS = 1 << 26         # SLIC_METRICS_MAX_CELLS: the dense n_classes x n_clusters int32 table
@@ -32,30 +33,20 @@ class HipClusterMetricsKernels:
     caller who knows its class counts passes a smaller bound (400 classes x 1000 clusters: max_cells=400_000, 1.6 MB)."""
 
     def __init__(self, max_cells=None):
-        _lib.load()
-        if not torch.cuda.is_available():
-            raise _lib.SlicError("cluster metrics need a gfx950 device (no CPU fallback)")
+        require_device("cluster metrics")
         if max_cells is not None and not 1 <= int(max_cells) <= MAX_CELLS:
             raise ValueError("max_cells must be in 1 .. {}, got {!r}".format(MAX_CELLS, max_cells))
         self.max_cells = MAX_CELLS if max_cells is None else int(max_cells)
 
-    def resident(self, labels):
-        """int32 device labels with unit stride (no copy when they already are); `labels` is an int32 host array or a device tensor"""
-        if torch.is_tensor(labels):
-            x = labels.detach().to(device="cuda", dtype=torch.int32)
-        else:
-            x = torch.from_numpy(np.ascontiguousarray(labels, dtype=np.int32)).cuda()
-        return x.contiguous()
+    resident = staticmethod(resident_labels)                    # int32 device labels with unit stride
 
     def metrics(self, labels_true, labels_pred):
         """-> the record (MI, H_true, H_pred, EMI, NMI, AMI, n_classes, n_clusters, status) as a host float64 array"""
         N = labels_true.shape[0]
         _lib.require_device(labels_true, labels_pred)
         max_cells = min(N * N, self.max_cells)
-        nbytes = _lib.load().slic_cluster_metrics_workspace_bytes(N, max_cells)
-        if nbytes == 0:
-            raise _lib.SlicError("cluster metrics: {} labels are outside what slic_cluster_metrics takes (1 <= N <= {})".format(N, MAX_N))
-        ws = _lib.workspace(nbytes, labels_true.device, tag="cluster_metrics")
+        ws = sized_workspace("slic_cluster_metrics_workspace_bytes", (N, max_cells), labels_true.device, "cluster_metrics",
+                             "cluster metrics: {} labels are outside what slic_cluster_metrics takes (1 <= N <= {})".format(N, MAX_N))
         rec = torch.empty(RECORD, dtype=torch.float64, device=labels_true.device)
         call("slic_cluster_metrics", ptr(labels_true), ptr(labels_pred), N, max_cells, ptr(rec), ptr(ws), stream())
         return rec.cpu().numpy()
@@ -134,22 +125,16 @@ class HipSilhouetteKernels:
     the device and the call does not synchronise, so the [max_clusters, D] fp32 matrix of cluster means is sized by the bound."""
 
     def __init__(self, max_clusters=None):
-        _lib.load()
-        if not torch.cuda.is_available():
-            raise _lib.SlicError("the silhouette needs a gfx950 device (no CPU fallback)")
+        require_device("the silhouette")
         if max_clusters is not None and int(max_clusters) < 2:
             raise ValueError("max_clusters must be at least 2, got {!r}".format(max_clusters))
         self.max_clusters = None if max_clusters is None else int(max_clusters)
 
     def resident_rows(self, X):
         """fp32 device rows with unit stride inside a row (a device tensor, also a row-strided view, is used in place)"""
-        if torch.is_tensor(X):
-            x = X.detach().to(device="cuda", dtype=torch.float32)
-        else:
-            x = torch.from_numpy(np.ascontiguousarray(X, dtype=np.float32)).cuda()
-        return x if x.stride(1) == 1 and x.stride(0) >= x.shape[1] else x.contiguous()
+        return resident_rows(X, "the silhouette")
 
-    resident_labels = HipClusterMetricsKernels.resident        # int32 device labels with unit stride
+    resident_labels = staticmethod(resident_labels)             # int32 device labels with unit stride
 
     def take(self, x, idx):
         """rows idx (a host int64 array) of a resident array"""
@@ -164,12 +149,10 @@ class HipSilhouetteKernels:
         N, D = X.shape
         _lib.require_device(X, labels)
         kmax = N - 1 if self.max_clusters is None else min(self.max_clusters, N - 1)
-        nbytes = _lib.load().slic_silhouette_workspace_bytes(N, D, kmax)
-        if nbytes == 0:
-            raise _lib.SlicError("silhouette: N = {}, D = {} are outside what slic_silhouette takes (3 <= N <= {}, 1 <= D <= {})".format(
-                N, D, MAX_N, SILHOUETTE_MAX_D))
         dev = X.device
-        ws = _lib.workspace(nbytes, dev, tag="silhouette")
+        ws = sized_workspace("slic_silhouette_workspace_bytes", (N, D, kmax), dev, "silhouette",
+                             "silhouette: N = {}, D = {} are outside what slic_silhouette takes (3 <= N <= {}, 1 <= D <= {})".format(
+                                 N, D, MAX_N, SILHOUETTE_MAX_D))
         rec = torch.empty(SILHOUETTE_RECORD, dtype=torch.float64, device=dev)
         f = torch.empty((3, N), dtype=torch.float32, device=dev) if rows else None
         near = torch.empty(N, dtype=torch.int32, device=dev) if rows else None

@@ -16,6 +16,7 @@ import torch
 
 from .. import _lib
 from .._lib import call, ptr, stream
+from ._device import require_device, resident_rows, sized_workspace
 
 _STATS = ("band_rechecks", "walk_band_rechecks", "core_rows", "n_clusters", "largest_cluster", "walk_steps", "walk_launches",
           "host_loop_clusters", "ms_prep", "ms_count", "ms_compact", "ms_link", "ms_number", "ms_border", "ms_core_dist", "ms_walk")
@@ -26,33 +27,21 @@ class HipOpticsKernels:
     methods (tests of the host logic on a GPU-less machine pass a NumPy one as an ARGUMENT; the product has no other)."""
 
     def __init__(self):
-        _lib.load()
-        if not torch.cuda.is_available():
-            raise _lib.SlicError("OPTICS needs a gfx950 device for its neighbour search (no CPU fallback)")
+        require_device("OPTICS")
         self.last_stats = None
 
     def resident(self, data):
         """fp32 device rows with unit column stride (no copy when they already are)"""
-        if torch.is_tensor(data):
-            x = data.detach().to(device="cuda", dtype=torch.float32)
-        else:
-            x = torch.as_tensor(np.ascontiguousarray(data, dtype=np.float32)).cuda()
-        if x.dim() != 2:
-            raise ValueError("OPTICS expects a 2-D array [n_samples, n_features], got shape {}".format(tuple(x.shape)))
-        if x.stride(1) != 1 or x.stride(0) < x.shape[1]:
-            x = x.contiguous()
-        return x
+        return resident_rows(data, "OPTICS")
 
     def optics(self, rows, max_eps, min_samples, walk=True):
         """-> (labels int32 [N], is_core bool [N], core_dist float32 [N], reachability float32 [N], predecessor int32 [N],
         ordering int32 [N], n_clusters) as host arrays; walk=False: labels only, the four walk arrays are None"""
         N, D = rows.shape
         _lib.require_device(rows)
-        nbytes = _lib.load().slic_optics_cosine_workspace_bytes(N, D, int(min_samples))
-        if nbytes == 0:
-            raise _lib.SlicError("OPTICS: {} x {} rows with min_samples = {} are outside what slic_optics_cosine takes (1 <= D <= 512, "
-                                 "2 <= min_samples <= min(N, 89), rows of int32 indices, < 4 GiB padded)".format(N, D, min_samples))
-        ws = _lib.workspace(nbytes, rows.device, tag="optics")
+        ws = sized_workspace("slic_optics_cosine_workspace_bytes", (N, D, int(min_samples)), rows.device, "optics",
+                             "OPTICS: {} x {} rows with min_samples = {} are outside what slic_optics_cosine takes (1 <= D <= 512, "
+                             "2 <= min_samples <= min(N, 89), rows of int32 indices, < 4 GiB padded)".format(N, D, min_samples))
         dev = rows.device
         ints = torch.empty(3 * N + 1, dtype=torch.int32, device=dev)                 # labels, predecessor, ordering, n_clusters
         flt = torch.empty(2 * N, dtype=torch.float32, device=dev)                    # core distances, reachability

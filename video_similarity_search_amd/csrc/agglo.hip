@@ -19,7 +19,7 @@
 // and one copy of the 32-byte record to the host, the round's only synchronisation.
 #include <stdlib.h>
 
-#include "common.h"
+#include "wg_scan.h"
 
 #define AG_SCAN_T 256                 // threads of a scan workgroup
 #define AG_SCAN_PER 4                 // ids per thread
@@ -117,64 +117,44 @@ __global__ __launch_bounds__(256) void agglo_init_state(const float* __restrict_
 // ---------------------------------------------------------------------------------------------------------------------------------
 // scan: act / pos / q from the live and stale flags
 // ---------------------------------------------------------------------------------------------------------------------------------
-// exclusive scan of one (x, y) pair per thread over the workgroup; *tx, *ty = the workgroup's totals.  All AG_SCAN_T threads call.
-__device__ __forceinline__ void agglo_block_scan(int& x, int& y, int* tx, int* ty) {
-  __shared__ int wx[AG_SCAN_T / 64], wy[AG_SCAN_T / 64];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  int ix = x, iy = y;                                           // inclusive within the wave
-  for (int o = 1; o < 64; o <<= 1) {
-    const int ux = __shfl_up(ix, o), uy = __shfl_up(iy, o);
-    if (lane >= o) { ix += ux; iy += uy; }
-  }
-  __syncthreads();                                              // a previous call's readers are done with wx / wy
-  if (lane == 63) { wx[w] = ix; wy[w] = iy; }
-  __syncthreads();
-  int bx = 0, by = 0, sx = 0, sy = 0;
-  for (int i = 0; i < AG_SCAN_T / 64; ++i) {
-    if (i < w) { bx += wx[i]; by += wy[i]; }
-    sx += wx[i]; sy += wy[i];
-  }
-  x = bx + ix - x;
-  y = by + iy - y;
-  *tx = sx; *ty = sy;
-}
+// the workgroup scans one (live, stale) pair per thread in one pass: slic_wg_scan<AG_SCAN_T, 2> (wg_scan.h)
 
 __global__ __launch_bounds__(AG_SCAN_T) void agglo_scan_count(int64_t N, AggloState s) {
   const int64_t i0 = (int64_t)blockIdx.x * AG_SCAN_BLK + (int64_t)threadIdx.x * AG_SCAN_PER;
-  int x = 0, y = 0;
+  __shared__ int sh[2 * (AG_SCAN_T / 64)];
+  int v[2] = {0, 0}, tot[2];
   for (int u = 0; u < AG_SCAN_PER; ++u)
-    if (i0 + u < N) { x += s.live[i0 + u]; y += s.stale[i0 + u]; }
-  int tx, ty;
-  agglo_block_scan(x, y, &tx, &ty);
-  if (threadIdx.x == 0) { s.bsum[2 * blockIdx.x] = tx; s.bsum[2 * blockIdx.x + 1] = ty; }
+    if (i0 + u < N) { v[0] += s.live[i0 + u]; v[1] += s.stale[i0 + u]; }
+  slic_wg_scan<AG_SCAN_T, 2>(v, sh, tot);
+  if (threadIdx.x == 0) { s.bsum[2 * blockIdx.x] = tot[0]; s.bsum[2 * blockIdx.x + 1] = tot[1]; }
 }
 
 // ONE workgroup: exclusive scan of the nb block totals, AG_SCAN_T at a time with a carry
 __global__ __launch_bounds__(AG_SCAN_T) void agglo_scan_blocks_kernel(int nb, AggloState s) {
+  __shared__ int sh[2 * (AG_SCAN_T / 64)];
   int cx = 0, cy = 0;
   for (int b0 = 0; b0 < nb; b0 += AG_SCAN_T) {
     const int b = b0 + threadIdx.x;
-    int x = b < nb ? s.bsum[2 * b] : 0, y = b < nb ? s.bsum[2 * b + 1] : 0;
-    int tx, ty;
-    agglo_block_scan(x, y, &tx, &ty);
-    if (b < nb) { s.boff[2 * b] = cx + x; s.boff[2 * b + 1] = cy + y; }
-    cx += tx; cy += ty;
+    int v[2] = {b < nb ? s.bsum[2 * b] : 0, b < nb ? s.bsum[2 * b + 1] : 0}, tot[2];
+    slic_wg_scan<AG_SCAN_T, 2>(v, sh, tot);
+    if (b < nb) { s.boff[2 * b] = cx + v[0]; s.boff[2 * b + 1] = cy + v[1]; }
+    cx += tot[0]; cy += tot[1];
   }
 }
 
 __global__ __launch_bounds__(AG_SCAN_T) void agglo_scan_write(int64_t N, AggloState s) {
   const int64_t i0 = (int64_t)blockIdx.x * AG_SCAN_BLK + (int64_t)threadIdx.x * AG_SCAN_PER;
+  __shared__ int sh[2 * (AG_SCAN_T / 64)];
   int lv[AG_SCAN_PER], st[AG_SCAN_PER];
-  int x = 0, y = 0;
+  int v[2] = {0, 0}, tot[2];
   for (int u = 0; u < AG_SCAN_PER; ++u) {
     lv[u] = i0 + u < N ? s.live[i0 + u] : 0;
     st[u] = i0 + u < N ? s.stale[i0 + u] : 0;
-    x += lv[u]; y += st[u];
+    v[0] += lv[u]; v[1] += st[u];
   }
-  int tx, ty;
-  agglo_block_scan(x, y, &tx, &ty);
-  x += s.boff[2 * blockIdx.x];
-  y += s.boff[2 * blockIdx.x + 1];
+  slic_wg_scan<AG_SCAN_T, 2>(v, sh, tot);
+  int x = v[0] + s.boff[2 * blockIdx.x];
+  int y = v[1] + s.boff[2 * blockIdx.x + 1];
   for (int u = 0; u < AG_SCAN_PER; ++u) {
     if (i0 + u >= N) break;
     if (lv[u]) { s.act[x] = (int32_t)(i0 + u); s.pos[i0 + u] = x; ++x; }

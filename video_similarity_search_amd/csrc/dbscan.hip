@@ -13,12 +13,12 @@
 //           hi is a neighbour, below lo is not, in between is decided in float64 from the raw rows (a per-lane pending list drained
 //           between accumulators).  Each hit adds to both rows: the row side in a register, the column side by ballot + one atomic
 //           per gallery row and tile.  The N x N matrix is never written.
-//   compact core flags, then one prefix scan gives the core list and the border-candidate list (non-core rows with a neighbour
-//           other than themselves: count >= 2); their rows are gathered into Xcb = [Xc; Xb].
+//   compact core flags, then one workgroup scan (slic_wg_scan) each gives the core list and the border-candidate list (non-core rows
+//           with a neighbour other than themselves: count >= 2); their rows are gathered into Xcb = [Xc; Xb].
 //   link    the same GEMM over Xc x Xc (upper triangle); a hit unites its two cores in parent[] by CAS, always hooking the larger
 //           root under the smaller, so a component's final root is its smallest member.  A tile whose 256 rows already share one
 //           root is skipped before its k loop; in the epilogue cached roots are compared before any atomic.
-//   number  pointer jumping to the roots, a prefix scan over the root flags gives every root its cluster number.
+//   number  pointer jumping to the roots, slic_wg_scan over the root flags gives every root its cluster number.
 //   border  Xb x Xc (full rectangle): a hit takes atomicMin of the core's root; the smallest root is the smallest cluster number.
 // Every decision is an integer fixed by the float64 rule, so labels, core flags and counts are the same on every run.
 // csrc/optics.hip runs the same passes (db_label_passes, declared in dbscan_shared.h with the pieces the two files share) with one more
@@ -337,9 +337,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 __global__ __launch_bounds__(DB_SCAN_T) void db_compact(const int* __restrict__ cnt, int N, int min_samples,
                                                         uint8_t* __restrict__ is_core, int32_t* __restrict__ labels,
                                                         int* __restrict__ core_idx, int* __restrict__ border_idx, int* __restrict__ meta) {
-  __shared__ int sh[DB_SCAN_T / 64 + 1];
-  const int chunk = (N + DB_SCAN_T - 1) / DB_SCAN_T;
-  const int beg = min(N, (int)threadIdx.x * chunk), end = min(N, beg + chunk);
+  __shared__ int sh[DB_SCAN_T / 64];
+  int beg, end;
+  slic_run_bounds(N, DB_SCAN_T, threadIdx.x, &beg, &end);
   int nc = 0, nb = 0;
   for (int i = beg; i < end; ++i) {
     const int c = cnt[i];
@@ -347,18 +347,18 @@ __global__ __launch_bounds__(DB_SCAN_T) void db_compact(const int* __restrict__ 
     nc += core ? 1 : 0;
     nb += !core && c >= 2 ? 1 : 0;
   }
-  int tc, tb;
-  int oc = db_block_scan(nc, sh, &tc);
-  int ob = db_block_scan(nb, sh, &tb);
+  int oc[1] = {nc}, ob[1] = {nb}, tc[1], tb[1];                  // one value at a time: a pair would double sh
+  slic_wg_scan<DB_SCAN_T, 1>(oc, sh, tc);
+  slic_wg_scan<DB_SCAN_T, 1>(ob, sh, tb);
   for (int i = beg; i < end; ++i) {
     const int c = cnt[i];
     const bool core = c >= min_samples;
     is_core[i] = core ? 1 : 0;
     labels[i] = -1;
-    if (core) core_idx[oc++] = i;
-    else if (c >= 2) border_idx[ob++] = i;
+    if (core) core_idx[oc[0]++] = i;
+    else if (c >= 2) border_idx[ob[0]++] = i;
   }
-  if (threadIdx.x == 0) { meta[1] = tc; meta[2] = tb; }
+  if (threadIdx.x == 0) { meta[1] = tc[0]; meta[2] = tb[0]; }
 }
 
 // Xcb = [Xn[core_idx]; Xn[border_idx]], parent[c] = c, best[b] = INT_MAX
@@ -396,17 +396,16 @@ __global__ __launch_bounds__(256) void db_compress(int* __restrict__ parent, con
 // cluster number of every root (roots in index order), *n_clusters
 __global__ __launch_bounds__(DB_SCAN_T) void db_number(const int* __restrict__ parent, const int* __restrict__ meta, int* __restrict__ cid,
                                                        int32_t* __restrict__ n_clusters) {
-  __shared__ int sh[DB_SCAN_T / 64 + 1];
+  __shared__ int sh[DB_SCAN_T / 64];
   const int nc = meta[1];
-  const int chunk = (nc + DB_SCAN_T - 1) / DB_SCAN_T;
-  const int beg = min(nc, (int)threadIdx.x * chunk), end = min(nc, beg + chunk);
-  int n = 0;
-  for (int c = beg; c < end; ++c) n += parent[c] == c ? 1 : 0;
-  int tot;
-  int o = db_block_scan(n, sh, &tot);
+  int beg, end;
+  slic_run_bounds(nc, DB_SCAN_T, threadIdx.x, &beg, &end);
+  int o[1] = {0}, tot[1];
+  for (int c = beg; c < end; ++c) o[0] += parent[c] == c ? 1 : 0;
+  slic_wg_scan<DB_SCAN_T, 1>(o, sh, tot);
   for (int c = beg; c < end; ++c)
-    if (parent[c] == c) cid[c] = o++;
-  if (threadIdx.x == 0) *n_clusters = tot;
+    if (parent[c] == c) cid[c] = o[0]++;
+  if (threadIdx.x == 0) *n_clusters = tot[0];
 }
 
 __global__ __launch_bounds__(256) void db_label_core(const int* __restrict__ parent, const int* __restrict__ cid, const int* __restrict__ meta,

@@ -1,7 +1,8 @@
-// What csrc/optics.hip shares with csrc/dbscan.hip: the float64 pair decision, the one-workgroup scan, the workspace layout of the label
-// passes and the passes themselves (db_label_passes: prep, count, compact, link, number, border).  The kernels stay in dbscan.hip.
+// What csrc/optics.hip shares with csrc/dbscan.hip: the float64 pair decision, the size of the one-workgroup scans (slic_wg_scan,
+// wg_scan.h), the workspace layout of the label passes and the passes themselves (db_label_passes: prep, count, compact, link, number,
+// border).  The kernels stay in dbscan.hip.
 #pragma once
-#include "common.h"
+#include "wg_scan.h"
 #include <math.h>
 
 #define DB_B 128              // rows per tile (both operands)
@@ -19,29 +20,6 @@ __device__ inline bool db_exact(const float* __restrict__ X, int ldx, int D, con
   double d = 1.0 - s * inv[a] * inv[b];
   d = fmin(fmax(d, 0.0), 2.0);
   return d <= eps;
-}
-
-// exclusive scan of one int per thread over a DB_SCAN_T-thread workgroup; returns the prefix, *total = the sum
-__device__ inline int db_block_scan(int v, int* sh, int* total) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  int x = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int y = __shfl_up(x, o);
-    if (lane >= o) x += y;
-  }
-  if (lane == 63) sh[w] = x;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int run = 0;
-    for (int i = 0; i < DB_SCAN_T / 64; ++i) { const int t = sh[i]; sh[i] = run; run += t; }
-    sh[DB_SCAN_T / 64] = run;
-  }
-  __syncthreads();
-  const int r = sh[w] + x - v;
-  *total = sh[DB_SCAN_T / 64];
-  __syncthreads();
-  return r;
 }
 
 struct DbLayout {

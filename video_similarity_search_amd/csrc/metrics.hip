@@ -8,17 +8,18 @@
 // Passes (one stream, no host synchronisation: every size that depends on the data is read from `meta` on the device):
 //   ids      per labelling: keys = label with the sign bit flipped (unsigned order = signed order); LSD radix sort, 8 passes of 4 bits,
 //            each thread owning CM_CHUNK consecutive keys (16 byte-wide counters packed in two 64-bit registers, so a pass is
-//            histogram -> one-workgroup scan -> stable scatter with no atomics); run heads of the sorted keys -> scan -> the sorted
-//            distinct values uniq[U] and their first positions start[U]; counts = differences of start (the marginal, exact);
-//            id[i] = lower bound of key[i] in uniq.
+//            histogram -> one-workgroup scan (slic_wg_scan_array, wg_scan.h) -> stable scatter with no atomics); run heads of the
+//            sorted keys -> scan -> the sorted distinct values uniq[U] and their first positions start[U]; counts = differences of
+//            start (the marginal, exact); id[i] = lower bound of key[i] in uniq.
 //   table    status = R * C > max_cells; clear R * C cells; n[id_true[i]][id_pred[i]] += 1 (int32 atomics: exact in any order).
 //   lgamma   L[x] = lgamma(x + 1), ln[x] = log(x) (ln[0] = 0) and T[x] = sum_{k < x} log1p(-k / N) (a fixed-order scan) for x = 0 .. N.
 //   MI, H    one term per cell / class, summed in the fixed order of the header.
 //   EMI      one thread per (class, cluster) cell walks n = max(1, a + b - N) .. min(a, b): five table look-ups, one division and one
 //            exp per term; cells are dealt round-robin to 1024 x 256 threads.  The work is sum_ij min(a_i, b_j) terms.
-//   finish   folds the four sets of 1024 partial sums and applies the NMI / AMI rules; writes the record.
+//   finish   folds (slic_wg_fold) the four sets of 1024 partial sums and applies the NMI / AMI rules; writes the record.
 // fp contraction is off for the whole file: a * b + c stays two roundings, which is what the fp64 check restates on the host.
 #include "label_ids.h"
+#include "wg_scan.h"
 #include <math.h>
 #include <float.h>
 
@@ -78,29 +79,9 @@ __global__ __launch_bounds__(CM_T) void cm_radix_scatter(const uint32_t* __restr
   }
 }
 
-// exclusive scan of data[0 .. n) in place by one workgroup (thread t owns a run of consecutive elements); *total = the sum
+// exclusive scan of data[0 .. n) in place by one workgroup; *total = the sum
 __global__ __launch_bounds__(CM_SCAN_T) void cm_scan(int* __restrict__ data, int n, int* __restrict__ total) {
-  __shared__ int s[CM_SCAN_T];
-  const int t = threadIdx.x;
-  const int per = (n + CM_SCAN_T - 1) / CM_SCAN_T;
-  const int lo = (int)min((int64_t)n, (int64_t)t * per), hi = min(n, lo + per);
-  int sum = 0;
-  for (int k = lo; k < hi; ++k) sum += data[k];
-  s[t] = sum;
-  __syncthreads();
-  for (int o = 1; o < CM_SCAN_T; o <<= 1) {
-    const int v = t >= o ? s[t - o] : 0;
-    __syncthreads();
-    s[t] += v;
-    __syncthreads();
-  }
-  int run = s[t] - sum;
-  for (int k = lo; k < hi; ++k) {
-    const int v = data[k];
-    data[k] = run;
-    run += v;
-  }
-  if (t == CM_SCAN_T - 1 && total) *total = s[CM_SCAN_T - 1];
+  slic_wg_scan_array<CM_SCAN_T, int>(data, n, total);
 }
 
 __global__ __launch_bounds__(CM_T) void cm_heads(const uint32_t* __restrict__ sorted, int N, int* __restrict__ flag) {
@@ -166,44 +147,9 @@ __global__ __launch_bounds__(CM_T) void cm_tables(int N, double* __restrict__ lg
   tl[x] = x < N ? log1p(-((double)x / (double)N)) : 0.0;       // cm_scan_f64 turns this into T(x) = sum_{k < x} log(1 - k / N)
 }
 
-// exclusive scan of data[0 .. n) in place by one workgroup, in a fixed order: thread t owns a run of ceil(n / 1024) consecutive
-// elements and adds them in ascending order from 0; the 1024 run sums are scanned by doubling (s[t] += s[t - o], o = 1 .. 512); a
-// run's elements are then re-added in ascending order onto the sum of the runs before it
+// the same in float64: the fixed order of slic_wg_scan_array is part of the contract (T(x) of the header)
 __global__ __launch_bounds__(CM_SCAN_T) void cm_scan_f64(double* __restrict__ data, int n) {
-  __shared__ double s[CM_SCAN_T];
-  const int t = threadIdx.x;
-  const int per = (n + CM_SCAN_T - 1) / CM_SCAN_T;
-  const int lo = (int)min((int64_t)n, (int64_t)t * per), hi = min(n, lo + per);
-  double sum = 0.0;
-  for (int k = lo; k < hi; ++k) sum += data[k];
-  s[t] = sum;
-  __syncthreads();
-  for (int o = 1; o < CM_SCAN_T; o <<= 1) {
-    const double v = t >= o ? s[t - o] : 0.0;
-    __syncthreads();
-    if (t >= o) s[t] += v;
-    __syncthreads();
-  }
-  double run = t > 0 ? s[t - 1] : 0.0;
-  for (int k = lo; k < hi; ++k) {
-    const double v = data[k];
-    data[k] = run;
-    run += v;
-  }
-}
-
-// the workgroup's 256 values folded by halving; every thread gets the sum
-__device__ __forceinline__ double cm_fold(double v, double* s) {
-  const int t = threadIdx.x;
-  s[t] = v;
-  __syncthreads();
-  for (int o = CM_T / 2; o > 0; o >>= 1) {
-    if (t < o) s[t] += s[t + o];
-    __syncthreads();
-  }
-  const double r = s[0];
-  __syncthreads();
-  return r;
+  slic_wg_scan_array<CM_SCAN_T, double>(data, n, nullptr);
 }
 
 __global__ __launch_bounds__(CM_T) void cm_mi(const int* __restrict__ table, const int* __restrict__ a, const int* __restrict__ b,
@@ -225,7 +171,7 @@ __global__ __launch_bounds__(CM_T) void cm_mi(const int* __restrict__ table, con
       acc += t;
     }
   }
-  const double r = cm_fold(acc, s);
+  const double r = slic_wg_fold<CM_T>(acc, s);
   if (threadIdx.x == 0) part[blockIdx.x] = r;
 }
 
@@ -243,7 +189,7 @@ __global__ __launch_bounds__(CM_T) void cm_entropy(const int* __restrict__ cnt, 
       acc += ((double)x / dN) * (ln[x] - lnN);
     }
   }
-  const double r = cm_fold(acc, s);
+  const double r = slic_wg_fold<CM_T>(acc, s);
   if (threadIdx.x == 0) part[blockIdx.x] = r;
 }
 
@@ -273,7 +219,7 @@ __global__ __launch_bounds__(CM_T) void cm_emi(const int* __restrict__ a, const 
       acc += cell;
     }
   }
-  const double r = cm_fold(acc, s);
+  const double r = slic_wg_fold<CM_T>(acc, s);
   if (threadIdx.x == 0) part[blockIdx.x] = r;
 }
 
@@ -283,7 +229,7 @@ __global__ __launch_bounds__(CM_T) void cm_finish(const double* __restrict__ par
   double sum[4];
   for (int q = 0; q < 4; ++q) {
     const double* p = part + q * CM_G;
-    sum[q] = cm_fold(((p[t] + p[t + CM_T]) + p[t + 2 * CM_T]) + p[t + 3 * CM_T], s);
+    sum[q] = slic_wg_fold<CM_T>(((p[t] + p[t + CM_T]) + p[t + 2 * CM_T]) + p[t + 3 * CM_T], s);
   }
   if (t != 0) return;
   const int R = meta[CM_R], C = meta[CM_C];

@@ -161,25 +161,24 @@ __global__ __launch_bounds__(DB_SCAN_T) void op_offsets(const int32_t* __restric
                                                         const int* __restrict__ cstart, const int32_t* __restrict__ n_clusters, int lds_rows,
                                                         int* __restrict__ segoff, int32_t* __restrict__ ordering, int* __restrict__ large,
                                                         int* __restrict__ ometa) {
-  __shared__ int sh[DB_SCAN_T / 64 + 1];
+  __shared__ int sh[DB_SCAN_T / 64];
   __shared__ int largest;
-  const int chunk = (N + DB_SCAN_T - 1) / DB_SCAN_T;
-  const int beg = min(N, (int)threadIdx.x * chunk), end = min(N, beg + chunk);
+  int beg, end;
+  slic_run_bounds(N, DB_SCAN_T, threadIdx.x, &beg, &end);
   if (threadIdx.x == 0) largest = 0;
-  int n = 0;
+  int o[1] = {0}, tot[1];
   for (int i = beg; i < end; ++i) {
     const int l = labels[i];
-    n += l < 0 ? 1 : (cstart[l] == i ? csize[l] : 0);
+    o[0] += l < 0 ? 1 : (cstart[l] == i ? csize[l] : 0);
   }
-  int tot;
-  int o = db_block_scan(n, sh, &tot);
+  slic_wg_scan<DB_SCAN_T, 1>(o, sh, tot);
   for (int i = beg; i < end; ++i) {
     const int l = labels[i];
-    if (l < 0) ordering[o++] = i;
-    else if (cstart[l] == i) { segoff[l] = o; o += csize[l]; }
+    if (l < 0) ordering[o[0]++] = i;
+    else if (cstart[l] == i) { segoff[l] = o[0]; o[0] += csize[l]; }
   }
   const int nc = *n_clusters;
-  for (int c = threadIdx.x; c < nc; c += DB_SCAN_T) atomicMax(&largest, csize[c]);      // (after db_block_scan's barriers)
+  for (int c = threadIdx.x; c < nc; c += DB_SCAN_T) atomicMax(&largest, csize[c]);      // (after slic_wg_scan's barriers)
   __syncthreads();
   if (largest > lds_rows) {
     const int thr = min(lds_rows, OP_LDS_SMALL);

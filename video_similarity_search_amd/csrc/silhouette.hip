@@ -21,11 +21,12 @@
 //            owns a row tile and walks a contiguous share of the cluster tiles (grid.y shares: the K-group split), the ring running
 //            on across tiles
 //   finish   combines the shares in ascending order (strict '<': the first dense id wins), a = own / (|C| - 1), b, s; writes the rows
-//   means    per-cluster and overall means of s in float64, in a fixed order (strided partial sums folded by halving)
+//   means    per-cluster and overall means of s in float64, in a fixed order (strided partial sums folded by halving: slic_wg_fold)
 // fp contraction is off for the whole file (Makefile: FLAGS_silhouette): every fused multiply-add is spelled fmaf, which is what the
 // test mirror restates.
 #include "label_ids.h"
 #include "mfma_ring.h"
+#include "wg_scan.h"
 #include <math.h>
 
 #define SIL_T 256
@@ -255,20 +256,6 @@ __global__ __launch_bounds__(SIL_T) void sil_finish(const float* __restrict__ po
   if (out_nearest) out_nearest[i] = nearest;
 }
 
-// the workgroup's 256 values folded by halving; every thread gets the sum
-__device__ __forceinline__ double sil_fold(double v, double* s) {
-  const int t = threadIdx.x;
-  s[t] = v;
-  __syncthreads();
-  for (int o = SIL_T / 2; o > 0; o >>= 1) {
-    if (t < o) s[t] += s[t + o];
-    __syncthreads();
-  }
-  const double r = s[0];
-  __syncthreads();
-  return r;
-}
-
 // slot j of the per-cluster outputs: the j-th scored cluster by ascending label (the ignored label takes no slot); slots past K: NaN, 0
 __global__ __launch_bounds__(SIL_T) void sil_cluster_means(const float* __restrict__ sbuf, const int* __restrict__ ord,
                                                           const int* __restrict__ start, const int* __restrict__ cnt,
@@ -291,7 +278,7 @@ __global__ __launch_bounds__(SIL_T) void sil_cluster_means(const float* __restri
   const int* o = ord + start[u];
   double acc = 0.0;
   for (int m = threadIdx.x; m < n; m += SIL_T) acc += (double)sbuf[o[m]];
-  const double tot = sil_fold(acc, sh);
+  const double tot = slic_wg_fold<SIL_T>(acc, sh);
   const int j = u - (ig >= 0 && u > ig ? 1 : 0);
   if (threadIdx.x == 0 && j < kmax) {
     if (cluster_mean) cluster_mean[j] = tot / (double)n;
@@ -308,14 +295,14 @@ __global__ __launch_bounds__(SIL_T) void sil_sum_part(const float* __restrict__ 
     for (int i = blockIdx.x * SIL_T + threadIdx.x; i < N; i += SIL_G * SIL_T)
       if (ids[i] != ig) acc += (double)sbuf[i];
   }
-  const double r = sil_fold(acc, sh);
+  const double r = slic_wg_fold<SIL_T>(acc, sh);
   if (threadIdx.x == 0) part[blockIdx.x] = r;
 }
 
 __global__ __launch_bounds__(SIL_T) void sil_record(const double* __restrict__ part, const int* __restrict__ meta, double* __restrict__ record) {
   __shared__ double sh[SIL_T];
   const int t = threadIdx.x;
-  const double sum = sil_fold(((part[t] + part[t + SIL_T]) + part[t + 2 * SIL_T]) + part[t + 3 * SIL_T], sh);
+  const double sum = slic_wg_fold<SIL_T>(((part[t] + part[t + SIL_T]) + part[t + 2 * SIL_T]) + part[t + 3 * SIL_T], sh);
   if (t != 0) return;
   const int status = meta[SIL_STATUS];
   record[0] = status ? (double)NAN : sum / (double)meta[SIL_NEFF];
