@@ -56,7 +56,10 @@ int slic_kmeans_cnorm(const float* C, int K, int D, int ldc, float* cnorm, void*
  * (_update_chunk_dense, _k_means_lloyd.pyx:189-213).  X: [N, D] row stride ldx (D % 8 == 0,
  * ldx % 4 == 0, 16-byte aligned).  If labels_old != NULL, *n_changed (int32, device) is
  * incremented by the number of rows whose label differs from labels_old (caller zeroes it).
- * best_score (optional, [N]) receives the winning score. */
+ * best_score (optional, [N]) receives the winning score.
+ * A row none of whose scores compares below +inf (a NaN among its values makes every score NaN; an infinity can make every
+ * score +inf) gets label 0, as sklearn's argmin does; the winning score of such a row is not specified.  Every other row is
+ * unaffected. */
 size_t slic_kmeans_assign_workspace_bytes(int64_t N, int K);
 int slic_kmeans_assign(const float* X, int64_t N, int D, int ldx, const float* C, int K, int ldc,
                        const float* cnorm, int32_t* labels, const int32_t* labels_old,
@@ -69,6 +72,13 @@ int slic_kmeans_permute_k8(const float* X, int64_t N, int D, int ldx, float* Xp,
 int slic_kmeans_assign_perm(const float* Xp, int64_t N, int D, int ldxp, const float* Cp, int K, int ldcp,
                             const float* cnorm, int32_t* labels, const int32_t* labels_old,
                             int32_t* n_changed, float* best_score, void* workspace, void* stream);
+/* Which kernels slic_kmeans_assign_perm (and the E-step inside slic_kmeans_lloyd_step / _lloyd_local) runs for a shape on the
+ * current device: the launch and this query call one decision function.  No device work, but the compute-unit count of the
+ * current device is part of the decision: without a device this returns an error with a message.
+ * out[6] = {route: 0 = 128 x 64 DMA tile, 1 = centroids in registers; k-tiles of 32 per point tile of the register kernel
+ * (4 / 8 / 16, else 0); point slices (gridDim.x of the register kernel, else 0); centroid blocks (gridDim.y); partial lists the
+ * combine pass reads; the compute-unit count used}. */
+int slic_kmeans_assign_perm_plan(int64_t N, int K, int D, int ldxp, int* out /* [6] */);
 
 /* M-step sums: sums[j,:] = sum of rows with label j, fp32, ASCENDING ROW ORDER (deterministic;
  * == sklearn's centers_new[label] += X[i] loop on one thread, _k_means_lloyd.pyx:215-218);

@@ -62,6 +62,15 @@ def assign(X, C, with_scores=False):
     return (labels, best, second) if with_scores else labels
 
 
+def scores(X, C):
+    """the whole [N, K] score matrix of `assign` (same expression, same chain)"""
+    X, C = _f32(X), _f32(C)
+    N, D = X.shape
+    out = np.empty((N, C.shape[0]), np.float32)
+    _lib().slic_oracle_scores(_p(X), ctypes.c_int64(N), D, _p(C), C.shape[0], _p(out))
+    return out
+
+
 def accumulate(X, labels, K, n_shards=1):
     X = _f32(X)
     labels = np.ascontiguousarray(labels, np.int32)

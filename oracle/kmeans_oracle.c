@@ -108,6 +108,36 @@ void slic_oracle_assign(const float* X, int64_t N, int D, const float* C, int K,
   free(cn);
 }
 
+/*
+ * The whole score matrix of the E-step: scores[i][j] = cnorm[j] - 2*dot(x_i,c_j), the expression and the chain of
+ * slic_oracle_assign (whose labels are the first minimum of every row).  For tests that model how a kernel merges its partial
+ * argmins; tests/test_kmeans_estep_cpu.py holds the two functions against each other.
+ */
+void slic_oracle_scores(const float* X, int64_t N, int D, const float* C, int K, float* scores) {
+  int Kp = (K + JB - 1) / JB * JB;
+  float* Ct = (float*)calloc((size_t)D * Kp, sizeof(float));
+  float* cn = (float*)malloc(sizeof(float) * Kp);
+  for (int j = 0; j < K; ++j)
+    for (int k = 0; k < D; ++k) Ct[(size_t)k * Kp + j] = C[(size_t)j * D + k];
+  slic_oracle_row_sqnorm_chain(C, K, D, cn);
+#pragma omp parallel for schedule(static)
+  for (int64_t i = 0; i < N; ++i) {
+    const float* x = X + (size_t)i * D;
+    for (int jb = 0; jb < Kp; jb += JB) {
+      float a[JB];
+      for (int j = 0; j < JB; ++j) a[j] = 0.0f;
+      for (int k = 0; k < D; ++k) {
+        const float xk = x[k];
+        const float* ct = Ct + (size_t)k * Kp + jb;
+        for (int j = 0; j < JB; ++j) a[j] = fmaf(xk, ct[j], a[j]);
+      }
+      for (int j = 0; j < JB && jb + j < K; ++j) scores[(size_t)i * K + jb + j] = cn[jb + j] - 2.0f * a[j];
+    }
+  }
+  free(Ct);
+  free(cn);
+}
+
 /* shard s of n_shards owns rows [s*per, min(N,(s+1)*per)), per = ceil(N/n_shards) */
 static void shard_range(int64_t N, int n_shards, int s, int64_t* lo, int64_t* hi) {
   int64_t per = (N + n_shards - 1) / n_shards;

@@ -275,10 +275,10 @@ def test_host_argument_rules():
 
 # ------------------------------------------------------------------ no entry point of kmeans.hip without a test module
 COVERED_ELSEWHERE = {
-    # the E-step, pinned bit for bit against the oracle
-    "slic_kmeans_assign_workspace_bytes": "test_kmeans_gpu", "slic_kmeans_assign": "test_kmeans_gpu",
-    "slic_kmeans_assign_perm": "test_kmeans_gpu",
-    "slic_kmeans_lloyd_local_workspace_bytes": "test_kmeans_gpu", "slic_kmeans_lloyd_local": "test_kmeans_gpu",
+    # the E-step, every entry point bit for bit against the oracle (its calls are methods of this module's Device)
+    "slic_kmeans_assign_workspace_bytes": "test_kmeans_estep_gpu", "slic_kmeans_assign": "test_kmeans_estep_gpu",
+    "slic_kmeans_assign_perm": "test_kmeans_estep_gpu", "slic_kmeans_assign_perm_plan": "test_kmeans_estep_gpu",
+    "slic_kmeans_lloyd_local_workspace_bytes": "test_kmeans_estep_gpu", "slic_kmeans_lloyd_local": "test_kmeans_estep_gpu",
     # the certified bf16 E-step (csrc/kmeans_bf16.h, included by kmeans.hip)
     "slic_kmeans_bf16_plan": "test_kmeans_bf16_cpu", "slic_kmeans_bf16_eps": "test_kmeans_bf16_cpu",
     "slic_kmeans_bf16_image": "test_kmeans_bf16_gpu", "slic_kmeans_assign_bf16_workspace_bytes": "test_kmeans_bf16_gpu",

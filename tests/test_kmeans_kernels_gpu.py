@@ -4,7 +4,8 @@ Entry points called by at least one case (COVERED: 16, and their 6 workspace que
   slic_kmeans_cnorm, slic_kmeans_permute_k8, slic_kmeans_accumulate, slic_kmeans_combine_shards, slic_kmeans_dist_to_assigned,
   slic_sum_f32_to_f64, slic_kmeans_select_far, slic_kmeans_apply_relocation, slic_kmeans_finalize, slic_kmeans_lloyd_step,
   slic_kmeans_lloyd_global, slic_col_stats, slic_sub_rowvec, slic_l2norm_rows, slic_kmeanspp_step, slic_cumsum_search
-  (slic_kmeans_lloyd_local's M-step half is slic_kmeans_accumulate's code; its E-step half belongs to test_kmeans_gpu.py).
+  (slic_kmeans_lloyd_local's M-step half is slic_kmeans_accumulate's code; the E-step entry points, whose calls `Device` also
+  holds, have their cases in tests/test_kmeans_estep_gpu.py).
 
 The checks are functions of a backend: `Device` calls the library; tests/test_kmeans_kernels_cpu.py runs the same functions with
 the NumPy mirror (tests/kmeans_kernels_ref.py) in the device's place, unmutated and with one defect at a time.  Importing this
@@ -122,7 +123,7 @@ class Device:
         self.tdt = {np.dtype(F32): torch.float32, np.dtype(F64): torch.float64, np.dtype(I32): torch.int32}
 
     def up(self, a, dtype=F32):
-        return None if a is None else self.t.from_numpy(np.ascontiguousarray(a, dtype=dtype)).cuda()
+        return None if a is None else self.t.from_numpy(np.array(a, dtype=dtype, order="C")).cuda()       # a copy: inputs may be read-only
 
     def out(self, shape, dtype=F32, data=None):
         """NaN / -7 (or `data`) in front of a guard tail"""
@@ -257,6 +258,56 @@ class Device:
         self.run("slic_kmeans_lloyd_global", self.up(parts, F64 if is64 else F32), int(is64), stride, W, self.up(C_old), K, D, sums,
                  counts, C_new, Cp_new, cn, sh, spherical, st)
         return self.np(sums, counts, C_new, Cp_new, cn, sh, st)
+
+    # -- E-step (the cases live in tests/test_kmeans_estep_gpu.py)
+    def estep_plan(self, N, K, D, ldx):
+        out = (ctypes.c_int * 6)()
+        assert self.lib.slic_kmeans_assign_perm_plan(N, K, D, ldx, out) == 0, self.lib.slic_last_error()
+        return tuple(out)
+
+    def _estep(self, name, x, N, D, ldx, c, K, ldc, cn, labels_old, nch0, want_score):
+        w = self.ws(self.lib.slic_kmeans_assign_workspace_bytes(N, K))
+        labels, nch = self.out((N,), I32), self.out((1,), I32, data=[nch0])
+        score = self.out((N,)) if want_score else None
+        self.run(name, x, N, D, ldx, c, K, ldc, self.up(cn), labels, self.up(labels_old, I32), nch, score, w)
+        labels, nch, score = self.np(labels, nch, score)
+        return labels, int(nch[0]), score
+
+    def estep_assign(self, Xb, D, Cb, xoff=0, coff=0, labels_old=None, nch0=12345, want_score=True):
+        """slic_kmeans_assign on the columns [xoff, xoff + D) of Xb and [coff, coff + D) of Cb"""
+        x, c = self.up(Xb), self.up(Cb)
+        return self._estep("slic_kmeans_assign", self.at(x, xoff), len(Xb), D, Xb.shape[1], self.at(c, coff), len(Cb), Cb.shape[1],
+                           R.cnorm(Cb[:, coff:coff + D]), labels_old, nch0, want_score)
+
+    def estep_assign_perm(self, Xb, D, Cb, xoff=0, coff=0, labels_old=None, nch0=12345, want_score=True, ldxp=None):
+        """slic_kmeans_assign_perm; Xb, Cb arrive in natural column order and are permuted here: on the host inside their
+        buffers, or (ldxp) X by slic_kmeans_permute_k8 into rows ldxp >= D + 4 apart that start 4 floats into a NaN buffer"""
+        Cp = np.array(Cb, F32)
+        Cp[:, coff:coff + D] = R.permute_k8(Cb[:, coff:coff + D])
+        c = self.up(Cp)
+        N = len(Xb)
+        if ldxp is None:
+            Xp = np.array(Xb, F32)
+            Xp[:, xoff:xoff + D] = R.permute_k8(Xb[:, xoff:xoff + D])
+            keep = self.up(Xp)
+            xp, ldx = self.at(keep, xoff), Xb.shape[1]
+        else:
+            assert ldxp >= D + 4
+            src, keep = self.up(Xb), self.out((N, ldxp))
+            self.run("slic_kmeans_permute_k8", self.at(src, xoff), N, D, Xb.shape[1], self.at(keep, 4), ldxp)
+            xp, ldx = self.at(keep, 4), ldxp
+        return self._estep("slic_kmeans_assign_perm", xp, N, D, ldx, self.at(c, coff), len(Cb), Cb.shape[1],
+                           R.cnorm(Cb[:, coff:coff + D]), labels_old, nch0, want_score)
+
+    def lloyd_local(self, X, C_old, labels_old, f64=False):
+        """labels, sums, counts and the n_changed pair of the payload"""
+        (N, D), K = X.shape, len(C_old)
+        w = self.ws(self.lib.slic_kmeans_lloyd_local_workspace_bytes(N, K))
+        labels, pay = self.out((N,), I32), self.out((K * D + K + 2,), F64 if f64 else F32)
+        self.run("slic_kmeans_lloyd_local", self.up(X), self.up(R.permute_k8(X)), N, D, D, self.up(R.permute_k8(C_old)),
+                 self.up(R.cnorm(C_old)), K, labels, self.up(labels_old, I32), pay, int(f64), w)
+        labels, pay = self.np(labels, pay)
+        return labels, pay[:K * D].reshape(K, D), pay[K * D:K * D + K], pay[K * D + K:]
 
     # -- k-means++ helpers
     def kpp_step(self, Xb, D, cand, closest):

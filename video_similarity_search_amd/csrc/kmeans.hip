@@ -1738,32 +1738,21 @@ extern "C" int slic_kmeans_permute_k8(const float* X, int64_t N, int D, int ldx,
   return SLIC_OK;
 }
 
-// bc (optional): also the M-step's per-1024-row-block label histogram [ceil(N / 1024)][K] (km_combine<true>)
-static int km_assign_perm_impl(const float* Xp, int64_t N, int D, int ldx, const float* Cp, int K,
-                               int ldc, const float* cnorm, int32_t* labels,
-                               const int32_t* labels_old, int32_t* n_changed, float* best_score,
-                               void* workspace, void* stream, int32_t* bc, int32_t* z0 = nullptr, int32_t* z1 = nullptr) {
-  SLIC_REQUIRE(Xp && Cp && cnorm && labels && workspace, "slic_kmeans_assign_perm: null pointer");
-  SLIC_REQUIRE(N > 0 && K > 0 && D > 0, "slic_kmeans_assign_perm: N=%lld K=%d D=%d", (long long)N, K, D);
-  SLIC_REQUIRE(D % 8 == 0 && ldx % 4 == 0 && ldc % 4 == 0 && ldx >= D && ldc >= D,
-               "slic_kmeans_assign_perm: need D %% 8 == 0 and 16-byte aligned rows (D=%d ldx=%d ldc=%d)", D, ldx, ldc);
-  SLIC_REQUIRE(((uintptr_t)Xp % 16) == 0 && ((uintptr_t)Cp % 16) == 0, "slic_kmeans_assign_perm: unaligned");
-  SLIC_REQUIRE((int64_t)KM_BP * ldx * 4 < (1ll << 31) && (int64_t)128 * ldc * 4 < (1ll << 31), "slic_kmeans_assign_perm: rows too long");
-  SLIC_REQUIRE(!labels_old || n_changed, "slic_kmeans_assign_perm: labels_old needs n_changed");
-  // tile / ring: 128 points x 64 centroids, 2 stages (measured best: a 64 x 64 tile with 2 x 2 waves fills the grid more evenly
-  // but loses the same few % inside the loop; 3 stages and 128 x 128 tiles were slower)
-  int G = (int)slic_cdiv(K, 64);
-  SlicCarver w(workspace);
-  float* pscore = w.take<float>((size_t)slic_cdiv(K, 32) * N);
-  int32_t* pidx = w.take<int32_t>((size_t)slic_cdiv(K, 32) * N);
-  hipStream_t st = S_(stream);
-  // Centroids in registers (km_assign_creg) when a 128-centroid block per workgroup wastes little (K = 500 -> 512) and the
-  // blocks x slices grid can cover the device: one residency round of 1-workgroup-per-CU workgroups.
-  const int cus = slic_device_cus();
-  if (!cus) {
-    slic_set_error("slic_kmeans_assign_perm: cannot query the device's compute units");
-    return SLIC_EHIP;
-  }
+// The route of the permuted-layout E-step, decided in ONE place: km_assign_perm_impl launches what this says and
+// slic_kmeans_assign_perm_plan reports it.
+// Centroids in registers (km_assign_creg) when a 128-centroid block per workgroup wastes little (K = 500 -> 512) and the
+// blocks x slices grid can cover the device: one residency round of 1-workgroup-per-CU workgroups.  Otherwise the 128 points x 64
+// centroids DMA tile, 2 stages (measured best: a 64 x 64 tile with 2 x 2 waves fills the grid more evenly but loses the same few %
+// inside the loop; 3 stages and 128 x 128 tiles were slower).
+struct KmPermPlan {
+  bool creg;        // km_assign_creg, else km_assign_dma<128, 2, 1, 2>
+  int nk;           // k-tiles of 32 per point tile of the register kernel (4 / 8 / 16), else 0
+  int slices;       // gridDim.x of the register kernel, else 0
+  int cblocks;      // gridDim.y: 128-centroid blocks (registers) or 64-centroid blocks (DMA tile)
+  int G;            // partial lists km_combine reads
+  int cus;
+};
+static KmPermPlan km_assign_perm_plan(int64_t N, int K, int D, int ldx, int cus) {
   const int ncb = (int)slic_cdiv(K, 128);
   const int64_t tiles = slic_cdiv(N, 128);
   int slices = ncb <= cus ? cus / ncb : 0;
@@ -1776,14 +1765,62 @@ static int km_assign_perm_impl(const float* Xp, int64_t N, int D, int ldx, const
                      slices >= 1 && (int64_t)ncb * 128 * 7 <= (int64_t)K * 8 &&          // <= 1/8 padding
                     tiles * 4 >= km_creg_min_quarter_tiles() * (int64_t)slices &&             // enough points per workgroup to pay for loading its centroids
                     (slic_cdiv(tiles, slices) * 128 + 128) * (int64_t)ldx * 4 < (1ll << 31);        // slice inside one resource
-  if (creg) {
+  KmPermPlan p;
+  p.creg = creg;
+  p.nk = !creg ? 0 : D > 256 ? 16 : D > 128 ? 8 : 4;
+  p.slices = creg ? slices : 0;
+  p.cblocks = creg ? ncb : (int)slic_cdiv(K, 64);
+  p.G = p.cblocks;                                             // one list per 128-centroid block / per 64-centroid wave column
+  p.cus = cus;
+  return p;
+}
+
+extern "C" int slic_kmeans_assign_perm_plan(int64_t N, int K, int D, int ldx, int* out) {
+  SLIC_REQUIRE(out, "slic_kmeans_assign_perm_plan: null pointer");
+  SLIC_REQUIRE(N > 0 && K > 0 && D > 0, "slic_kmeans_assign_perm_plan: N=%lld K=%d D=%d", (long long)N, K, D);
+  SLIC_REQUIRE(D % 8 == 0 && ldx % 4 == 0 && ldx >= D, "slic_kmeans_assign_perm_plan: need D %% 8 == 0 and 16-byte aligned rows (D=%d ldx=%d)",
+               D, ldx);
+  SLIC_REQUIRE((int64_t)KM_BP * ldx * 4 < (1ll << 31), "slic_kmeans_assign_perm_plan: rows too long");
+  const int cus = slic_device_cus();
+  if (!cus) {
+    slic_set_error("slic_kmeans_assign_perm_plan: cannot query the device's compute units");
+    return SLIC_EHIP;
+  }
+  const KmPermPlan p = km_assign_perm_plan(N, K, D, ldx, cus);
+  out[0] = p.creg ? 1 : 0; out[1] = p.nk; out[2] = p.slices; out[3] = p.cblocks; out[4] = p.G; out[5] = p.cus;
+  return SLIC_OK;
+}
+
+// bc (optional): also the M-step's per-1024-row-block label histogram [ceil(N / 1024)][K] (km_combine<true>)
+static int km_assign_perm_impl(const float* Xp, int64_t N, int D, int ldx, const float* Cp, int K,
+                               int ldc, const float* cnorm, int32_t* labels,
+                               const int32_t* labels_old, int32_t* n_changed, float* best_score,
+                               void* workspace, void* stream, int32_t* bc, int32_t* z0 = nullptr, int32_t* z1 = nullptr) {
+  SLIC_REQUIRE(Xp && Cp && cnorm && labels && workspace, "slic_kmeans_assign_perm: null pointer");
+  SLIC_REQUIRE(N > 0 && K > 0 && D > 0, "slic_kmeans_assign_perm: N=%lld K=%d D=%d", (long long)N, K, D);
+  SLIC_REQUIRE(D % 8 == 0 && ldx % 4 == 0 && ldc % 4 == 0 && ldx >= D && ldc >= D,
+               "slic_kmeans_assign_perm: need D %% 8 == 0 and 16-byte aligned rows (D=%d ldx=%d ldc=%d)", D, ldx, ldc);
+  SLIC_REQUIRE(((uintptr_t)Xp % 16) == 0 && ((uintptr_t)Cp % 16) == 0, "slic_kmeans_assign_perm: unaligned");
+  SLIC_REQUIRE((int64_t)KM_BP * ldx * 4 < (1ll << 31) && (int64_t)128 * ldc * 4 < (1ll << 31), "slic_kmeans_assign_perm: rows too long");
+  SLIC_REQUIRE(!labels_old || n_changed, "slic_kmeans_assign_perm: labels_old needs n_changed");
+  SlicCarver w(workspace);
+  float* pscore = w.take<float>((size_t)slic_cdiv(K, 32) * N);
+  int32_t* pidx = w.take<int32_t>((size_t)slic_cdiv(K, 32) * N);
+  hipStream_t st = S_(stream);
+  const int cus = slic_device_cus();
+  if (!cus) {
+    slic_set_error("slic_kmeans_assign_perm: cannot query the device's compute units");
+    return SLIC_EHIP;
+  }
+  const KmPermPlan plan = km_assign_perm_plan(N, K, D, ldx, cus);
+  const int G = plan.G;
+  if (plan.creg) {
     const size_t lds = (size_t)4 * 128 * SLIC_RT_BK * sizeof(float) + 4 * 128 * 2 * sizeof(float);     // the ring + the tile's four pair lists
-    dim3 grid((unsigned)slices, (unsigned)ncb);
-    const auto kern = D > 256 ? km_assign_creg<16, 4> : D > 128 ? km_assign_creg<8, 4> : km_assign_creg<4, 4>;
+    dim3 grid((unsigned)plan.slices, (unsigned)plan.cblocks);
+    const auto kern = plan.nk == 16 ? km_assign_creg<16, 4> : plan.nk == 8 ? km_assign_creg<8, 4> : km_assign_creg<4, 4>;
     SLIC_LDS_LIMIT(kern, lds);
     kern<<<grid, dim3(256), lds, st>>>(Xp, N, D, ldx, Cp, K, ldc, cnorm, pscore, pidx, z0, z1);
     SLIC_LAUNCH_CHECK();
-    G = ncb;                                                   // one list per 128-centroid block
   } else {
     int rc = launch_assign_dma<128, 2, 1, 2>(Xp, N, D, ldx, Cp, K, ldc, cnorm, pscore, pidx, st, z0, z1);
     if (rc) return rc;
