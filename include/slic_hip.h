@@ -1020,6 +1020,8 @@ int slic_clip_transform_apply(const void* table, const void* table_host, size_t 
  *                f64 h[10]          SGD : lr, momentum, 1 - dampening, weight_decay
  *                                   Adam: lr / bc1, 1 - beta1, beta2, 1 - beta2, eps, weight_decay, sqrt(bc2), bc = 1 - beta^step
  *                                   EMA : m, 1 - m
+ *                                   LARS: lr, momentum, trust_coefficient (> 0), weight_decay
+ *                                   the gradient-only operations (norm modes 1 and 2, scale) read g, n and flags alone: p may be 0
  *                                   computed by the caller in double, rounded to fp32 once on the device
  *   desc_host  the host copy of desc, validated before every launch (pointers, alignment against the flag, state present)
  * Formulas and the rounding of the chains (explicit fmaf, no other contraction): header comment of csrc/optim.hip.
@@ -1029,13 +1031,41 @@ int slic_clip_transform_apply(const void* table, const void* table_host, size_t 
 #define SLIC_MT_HYPER 10
 #define SLIC_MT_VEC 1
 #define SLIC_MT_NESTEROV 2
-#define SLIC_MT_FIRST 4      /* SGD: this tensor's first step, buf = g' */
+#define SLIC_MT_FIRST 4      /* SGD, LARS: this tensor's first step, buf = g' */
+#define SLIC_MT_ADAPT 8      /* LARS only: the update is scaled by the tensor's trust ratio; every other operation rejects the flag */
 /* chunk length in elements (a multiple of 4) */
 int slic_multi_tensor_chunk(void);
 /* all_first != 0: every tensor is on its first step (as if each carried SLIC_MT_FIRST), so the table of step 1 serves step 2 */
 int slic_multi_sgd(const void* map, int n_items, const void* desc, const void* desc_host, int n_tensors, int all_first, void* stream);
 int slic_multi_adam(const void* map, int n_items, const void* desc, const void* desc_host, int n_tensors, void* stream);
 int slic_multi_ema(const void* map, int n_items, const void* desc, const void* desc_host, int n_tensors, void* stream);
+/* Per-tensor norms over the same two tables, as two launches, and what reads them.  Deterministic: no floating-point atomics, a fixed
+ * summation order, so the same inputs give the same bits (order and rounding: header comment of csrc/optim.hip).
+ *   slic_multi_sqnorm     partials [n_items][2] doubles (8-byte aligned), one pair per work item, every pair written:
+ *                           SLIC_MT_NORM_LARS      {sum p^2, sum u^2}, u = weight_decay != 0 ? fmaf(weight_decay, p, g) : g in fp32 (LARS table)
+ *                           SLIC_MT_NORM_GRAD_L2   {0, sum g^2}
+ *                           SLIC_MT_NORM_GRAD_INF  {0, max |g|}, NaN if an element is
+ *                         elements widened to double, squares and sums in double
+ *   slic_multi_norm_fold  the same mode and table; n_items must be the work items the tensors make.  norms [3][n_tensors] fp32 (8-byte
+ *                         aligned): wnorm, unorm, q, each rounded once from double; q = (wnorm > 0 && unorm > 0) ?
+ *                         trust_coefficient * wnorm / unorm : 1 in SLIC_MT_NORM_LARS, 1 otherwise.  The gradient modes also write total [2] fp32
+ *                         (8-byte aligned; may be NULL in SLIC_MT_NORM_LARS): the norm over all tensors, and the coefficient
+ *                         min(max_norm * (1 / (total + 1e-6)), 1) in fp32 as torch.nn.utils.clip_grad_norm_ rounds it (NaN stays NaN).
+ *                         max_norm must be finite.
+ *   slic_multi_lars       the LARS step: u = g + wd p; v = SLIC_MT_ADAPT ? ratios[tensor] u : u; buf = first ? v : mom buf + v; p -= lr buf.
+ *                         ratios: the q row of norms (device; may be NULL when no tensor carries SLIC_MT_ADAPT).  A tensor without the
+ *                         flag is slic_multi_sgd's chain with dampening 0 and no nesterov, bit for bit.
+ *   slic_multi_scale      g *= total[1], read on the device; writes nothing where total[1] >= 1 (NaN is not).  Gradient-only table. */
+#define SLIC_MT_NORM_LARS 0
+#define SLIC_MT_NORM_GRAD_L2 1
+#define SLIC_MT_NORM_GRAD_INF 2
+int slic_multi_sqnorm(const void* map, int n_items, const void* desc, const void* desc_host, int n_tensors, int mode, double* partials,
+                      void* stream);
+int slic_multi_norm_fold(const void* desc, const void* desc_host, int n_tensors, int n_items, const double* partials, int mode,
+                         double max_norm, float* norms, float* total, void* stream);
+int slic_multi_lars(const void* map, int n_items, const void* desc, const void* desc_host, int n_tensors, int all_first, const float* ratios,
+                    void* stream);
+int slic_multi_scale(const void* map, int n_items, const void* desc, const void* desc_host, int n_tensors, const float* total, void* stream);
 
 #ifdef __cplusplus
 }

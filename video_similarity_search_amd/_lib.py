@@ -210,6 +210,10 @@ SIGNATURES = {
     "slic_multi_sgd": (I, [P, I, P, P, I, I, P]),
     "slic_multi_adam": (I, [P, I, P, P, I, P]),
     "slic_multi_ema": (I, [P, I, P, P, I, P]),
+    "slic_multi_sqnorm": (I, [P, I, P, P, I, I, P, P]),
+    "slic_multi_norm_fold": (I, [P, P, I, I, P, I, Dbl, P, P, P]),
+    "slic_multi_lars": (I, [P, I, P, P, I, I, P, P]),
+    "slic_multi_scale": (I, [P, I, P, P, I, P, P]),
 }
 
 
