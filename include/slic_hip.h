@@ -1067,6 +1067,41 @@ int slic_multi_lars(const void* map, int n_items, const void* desc, const void* 
                     void* stream);
 int slic_multi_scale(const void* map, int n_items, const void* desc, const void* desc_host, int n_tensors, const float* total, void* stream);
 
+/* Exact t-SNE in two dimensions over a dense N x N fp32 matrix, after sklearn 1.7.2's TSNE(method='exact') (csrc/tsne.hip), and the
+ * centred Gram matrix of PCA.  2 <= N <= SLIC_TSNE_MAX_N.  No floating-point atomics: every sum has one fixed order, two runs agree
+ * bit for bit.  None of the calls synchronises.
+ *   sqdist       d2 [N, N]: d2[i][j] = sum_k (x_ik - x_jk)^2, k ascending, fp32 (X [N, D], row stride ldx >= D, any D >= 1).  Equal
+ *                rows give exactly 0; the diagonal is 0.
+ *   cond_p       in place over d2: row i becomes p_j|i = exp(-beta_i d_ij) / sum_{k != i} exp(-beta_i d_ik), p_i|i = 0, with beta_i
+ *                found by _binary_search_perplexity's rule (at most 100 steps from beta = 1: doubling / halving / bisection until the
+ *                entropy is within 1e-5 of log(perplexity)), evaluated on d - min_{k != i} d_ik (the same p, sum >= 1) with the
+ *                row sums in double.  beta [N] fp32: the beta of the last step evaluated.
+ *   symmetrize   in place: P <- max((P + P^T) / sum(P + P^T), DBL_EPSILON) off the diagonal, 0 on it; P == P^T bit for bit.
+ *   step         one iteration of _gradient_descent on Y [N, 2] with its state update [N, 2], gains [N, 2] (all fp32, in place):
+ *                w_ij = 1 / (1 + |y_i - y_j|^2), Z = sum_{i != j} w_ij, grad_i = 4 sum_j (e P_ij w_ij - w_ij^2 / Z)(y_i - y_j);
+ *                gains += 0.2 where update * grad < 0, else *= 0.8, floor 0.01; update = momentum update - learning_rate gains grad;
+ *                Y += update.  grad_out [N, 2] (may be NULL): grad before the gains.  record (SLIC_TSNE_RECORD doubles): Z; the KL
+ *                divergence sum_{i != j} e P_ij log(e P_ij Z / w_ij) of the Y the call read (NaN unless want_kl); |gains grad|_2 (the
+ *                norm _gradient_descent tests); sum_{i != j} P_ij (NaN unless want_kl).  Three launches.
+ *   gram         G [D, D] double = sum_i (x_i - mean)(x_i - mean)^T, products and sums in double, rows ascending inside each of
+ *                `shares` equal row ranges, the ranges added in order.  partial: [shares, D, D] doubles of scratch.
+ * The workspace of symmetrize and step: slic_tsne_workspace_bytes, 0 for an N outside the limits. */
+#define SLIC_TSNE_MAX_N 65536
+#define SLIC_TSNE_GRAM_MAX_D 8192
+#define SLIC_TSNE_RECORD 4
+#define SLIC_TSNE_REC_Z 0
+#define SLIC_TSNE_REC_KL 1
+#define SLIC_TSNE_REC_GRAD_NORM 2
+#define SLIC_TSNE_REC_SUM_P 3
+size_t slic_tsne_workspace_bytes(int64_t N);
+int slic_tsne_sqdist(const float* X, int64_t N, int D, int64_t ldx, float* d2, void* stream);
+int slic_tsne_cond_p(float* P, int64_t N, double perplexity, float* beta, void* stream);
+int slic_tsne_symmetrize(float* P, int64_t N, void* workspace, void* stream);
+int slic_tsne_step(const float* P, int64_t N, float exaggeration, float momentum, float learning_rate, int want_kl, float* Y,
+                   float* update, float* gains, float* grad_out, double* record, void* workspace, void* stream);
+int slic_tsne_gram(const float* X, int64_t N, int D, int64_t ldx, const double* mean, int shares, double* partial, double* G,
+                   void* stream);
+
 #ifdef __cplusplus
 }
 #endif

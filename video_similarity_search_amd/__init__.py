@@ -14,9 +14,21 @@ path behind the reference's Python call surface (rvl-lab-utoronto/video_similari
     coclr_classify.train_one_epoch / validate / test_10crop / test_retrieval
                                             <- coclr_classify.py:395-830
     misc.distributed_helper                 <- misc/distributed_helper.py
+    tsne.tsne_projection, manifold.TSNE, decomposition.PCA
+                                            <- tsne.py (the data path: class subset, PCA(50), exact t-SNE; no plotting)
 
 All arithmetic runs in hand-written HIP kernels in csrc/ behind the C ABI of include/slic_hip.h
 (libslic_hip.so, loaded with ctypes).  There is no CPU fallback: importing a compute entry point
 without the built library, or calling it without a gfx950 device, raises.
 """
 __version__ = "0.1.0"
+
+_EXPORTS = {"TSNE": "manifold", "PCA": "decomposition", "tsne_projection": "tsne"}
+
+
+def __getattr__(name):
+    # resolved on first use: importing the package alone loads neither torch nor the library
+    if name in _EXPORTS:
+        import importlib
+        return getattr(importlib.import_module("." + _EXPORTS[name], __name__), name)
+    raise AttributeError("module {!r} has no attribute {!r}".format(__name__, name))

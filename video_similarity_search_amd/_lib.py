@@ -214,6 +214,13 @@ SIGNATURES = {
     "slic_multi_norm_fold": (I, [P, P, I, I, P, I, Dbl, P, P, P]),
     "slic_multi_lars": (I, [P, I, P, P, I, I, P, P]),
     "slic_multi_scale": (I, [P, I, P, P, I, P, P]),
+    # exact t-SNE (dense P) and the centred Gram matrix of PCA
+    "slic_tsne_workspace_bytes": (c_size_t, [L]),
+    "slic_tsne_sqdist": (I, [P, L, I, L, P, P]),
+    "slic_tsne_cond_p": (I, [P, L, Dbl, P, P]),
+    "slic_tsne_symmetrize": (I, [P, L, P, P]),
+    "slic_tsne_step": (I, [P, L, F, F, F, I, P, P, P, P, P, P, P]),
+    "slic_tsne_gram": (I, [P, L, I, L, P, I, P, P, P]),
 }
 
 
