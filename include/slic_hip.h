@@ -747,6 +747,58 @@ int slic_optics_cosine(const float* X, int64_t N, int ldx, int D, double max_eps
 int slic_optics_cosine_stats(const void* workspace, double* out_host /* [16] */, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * HDBSCAN, cosine metric (sklearn.cluster.HDBSCAN(min_cluster_size, min_samples, metric='cosine') of sklearn 1.7: density clusters with
+ * noise and no radius to tune).  The device does what is O(N^2 D): core distances and the minimum spanning tree of the mutual
+ * reachability weights, by Boruvka rounds; the caller keeps the components between the rounds and turns the N - 1 edges into labels
+ * (clustering/hdbscan.py).  Rules:
+ *   1. d(i, j) = clip(1 - x^_i . x^_j, 0, 2) on the L2-normalised rows.  A zero row is at distance 1 from every other row, as in
+ *      slic_dbscan_cosine's rule 1.  d(i, i) = 0.
+ *   2. core(i) = the min_samples-th smallest entry of row i of d INCLUDING the diagonal zero: sklearn's
+ *      np.partition(D, min_samples - 1)[:, min_samples - 1] (min_samples = 1: core = 0).
+ *   3. w(i, j) = max(d(i, j), core(i), core(j)).
+ *   4. The tree is the minimum spanning tree of w under the total order (w, min(i, j), max(i, j)), which makes it unique.
+ *   5. From the tree, on the host, by the HDBSCAN definition: the single-linkage tree of the edges sorted in that order, the condensed
+ *      tree with min_cluster_size and lambda = 1 / height, stability, 'eom' or 'leaf' selection with allow_single_cluster,
+ *      cluster_selection_epsilon, labels_ (noise = -1) and probabilities_.
+ *   6. Clusters are numbered 0, 1, ... by their smallest row (sklearn numbers by condensed-tree id: the partitions are equal).
+ * Arithmetic.  The searches see fp32: the rows are normalised with a float64 inverse norm and rounded to fp32 (zero-padded to Dp = D
+ * rounded up to 8), a score is the fp32 MFMA dot of two such rows, |score - exact| <= (Dp + 2) 2^-24.  Every value that is REPORTED
+ * is float64 of the raw fp32 rows: the dot of the pair (lower row first; lane l of a wave takes elements l, l + 64, ... by fma, then an
+ * xor butterfly: one fixed order, the same from either end of the pair) times the float64 inverse norms.
+ *   slic_hdbscan_core          prep, then slic_cosine_topk of the rows against themselves (self_mask = 0, k = min_samples: the row itself is
+ *                              in its list, rule 2's diagonal) and core_dist[i] (device, float64 [N]) = the float64 distance to the
+ *                              list's last row (0 when that is the row itself).  The normalised rows and an fp32 copy of core_dist stay
+ *                              in the workspace: the state of the two calls below.
+ *   slic_hdbscan_round         one Boruvka round, the hot path: a streamed rows x rows^T pass (the MFMA row-tile ring) that finds for every
+ *                              row i min_j w32(i, j) over the rows j with comp[j] != comp[i], w32 = max(fp32 d, fp32 core(i), fp32
+ *                              core(j)), a tie going to the smaller j; then for every component c in [0, C) its least (w32, lo, hi)
+ *                              over its rows, (lo, hi) = (min, max) of (i, j): out_i[c] = lo, out_j[c] = hi, out_w[c] = w32 (device
+ *                              arrays of C; -1, -1, +inf for a component with no foreign row, i.e. C == 1).  comp: device int32 [N]
+ *                              with values in [0, C) (a row with another value proposes nothing).  row_best: NULL, or a device array
+ *                              of N that receives (bits of w32 << 32) | j per row (all ones: no foreign row).  All reductions are
+ *                              64-bit integer atomicMin: order-independent.  fp32 scores seen from the two ends of a pair may differ
+ *                              in the last bit, so the candidates of a round may close a cycle: the caller applies them through
+ *                              union-find in the order (float64 w, lo, hi) and drops an edge whose ends are already connected; every
+ *                              component still proposes an edge that leaves it, so the rounds end with a spanning tree after at most
+ *                              ceil(log2 N) of them.  With exact weights every candidate is an edge of rule 4's tree.
+ *   slic_hdbscan_edge_weights  out[e] (device, float64 [M]) = rule 3's w in float64 for pairs[e] = (i, j) (device int32 [M, 2]), one wave
+ *                              per pair; NaN for a pair outside the rows.  core_dist: slic_hdbscan_core's output.
+ *   slic_hdbscan_stats         out_host[0] = rounds since the last slic_hdbscan_core, [1] rows searched by the last round, [2] ms of the
+ *                              core call, [3] ms of all rounds, [4] of the last round, [5] of its streamed pass alone when
+ *                              SLIC_HDBSCAN_TIMING=1 was set at the calls (else -1; the timed calls synchronise).  Measurement only.
+ * No float atomics: two runs are bit-equal.  The N x N matrix is never written; the workspace is O(N * Dp + N * min_samples).
+ * X: [N, D] fp32, row stride ldx >= D.  SLIC_EINVAL for N < 2, D outside [1, 512], min_samples outside [1, min(N, 88)] (the search's list
+ * length), rows beyond slic_dbscan_cosine's limits (int32 row indices, < 4 GiB padded), C outside [1, N].  N, D and min_samples of the
+ * later calls are those of the slic_hdbscan_core call that filled the workspace. */
+size_t slic_hdbscan_workspace_bytes(int64_t N, int D, int min_samples);       /* 0 for arguments slic_hdbscan_core rejects */
+int slic_hdbscan_core(const float* X, int64_t N, int ldx, int D, int min_samples, double* core_dist, void* workspace, void* stream);
+int slic_hdbscan_round(void* workspace, int64_t N, int D, int min_samples, const int32_t* comp, int C, int32_t* out_i, int32_t* out_j,
+                       float* out_w, uint64_t* row_best, void* stream);
+int slic_hdbscan_edge_weights(const float* X, int64_t N, int ldx, int D, int min_samples, const double* core_dist, const int32_t* pairs,
+                              int64_t M, double* out, void* workspace, void* stream);
+int slic_hdbscan_stats(double* out_host /* [6] */);
+
+/* ------------------------------------------------------------------------------------------
  * Average-linkage agglomerative clustering, cosine metric, cut by a distance threshold (clustering/cluster_masks.py:49-54 ->
  * sklearn.cluster.AgglomerativeClustering(n_clusters=None, linkage='average', distance_threshold=t, affinity='cosine')).
  * The rows are L2-normalised (slic_normalize_rows) and zero-padded to Dp = D rounded up to 8.  A cluster is the sum S of its unit rows and

@@ -163,6 +163,11 @@ SIGNATURES = {
     "slic_optics_cosine_workspace_bytes": (c_size_t, [L, I, I]),
     "slic_optics_cosine": (I, [P, L, I, I, Dbl, I, P, P, P, P, P, P, P, P, P]),
     "slic_optics_cosine_stats": (I, [P, P, P]),
+    "slic_hdbscan_workspace_bytes": (c_size_t, [L, I, I]),
+    "slic_hdbscan_core": (I, [P, L, I, I, I, P, P, P]),
+    "slic_hdbscan_round": (I, [P, L, I, I, P, I, P, P, P, P, P]),
+    "slic_hdbscan_edge_weights": (I, [P, L, I, I, I, P, P, L, P, P, P]),
+    "slic_hdbscan_stats": (I, [P]),
     # average-linkage agglomerative clustering (cosine, distance threshold)
     "slic_agglo_workspace_bytes": (c_size_t, [L, I]),
     "slic_agglo_start": (I, [P, L, I, I, P, P, P]),

@@ -6,14 +6,15 @@ Same names, argument meaning, prints and return type (np.ndarray[N] labels).  me
 (SURVEY.md §8 A5/A6), method='finch' (§8f row 1: the method the shipped configs select) and
 method='DBSCAN' (cosine, clustering/dbscan.py) run on the GPU, and so does method='Agglomerative' (average linkage, cosine,
 clustering/agglomerative.py) once the caller states its distance_threshold, and method='OPTICS' (cosine, cluster_method='dbscan',
-clustering/optics.py) once the caller states its max_eps.
+clustering/optics.py) once the caller states its max_eps.  method='HDBSCAN' (cosine, clustering/hdbscan.py; not in the reference) is the
+density method that needs no radius.
 """
 import torch
 
 from ._device import require_device, resident_rows
 from .kmeans_hip import HipKernels, KMeans
 
-_METHODS = ['DBSCAN', 'Agglomerative', 'OPTICS', 'kmeans', 'spherical_kmeans', 'finch']
+_METHODS = ['DBSCAN', 'Agglomerative', 'OPTICS', 'kmeans', 'spherical_kmeans', 'finch', 'HDBSCAN']
 
 
 def _to_device(embeddings):
@@ -37,7 +38,7 @@ def preprocess_features_kmeans(data, kernels=None):
 
 def fit_cluster(embeddings, method='Agglomerative', k=1000, l2normalize=True, finch_partition=0,
                 n_init=10, init='k-means++', process_group=None, random_state=None, kernels=None, exchange=None,
-                *, eps=0.14, min_samples=None, distance_threshold=None, max_eps=None, precision=None):
+                *, eps=0.14, min_samples=None, distance_threshold=None, max_eps=None, precision=None, min_cluster_size=5):
     """Reference signature + keyword-only extras (n_init / init / process_group / random_state / kernels / exchange / eps /
     min_samples) that default to the reference's behaviour: KMeans(n_clusters=k, n_init=10).fit(embeddings).labels_, and for
     method='DBSCAN' DBSCAN(eps=0.14, min_samples=2, metric='cosine').fit(embeddings).labels_ (noise = -1; l2normalize does not
@@ -50,6 +51,9 @@ def fit_cluster(embeddings, method='Agglomerative', k=1000, l2normalize=True, fi
     (clustering/optics.py; `kernels` is then an OPTICS provider).  The reference's e is the hand-tuned 0.20 (cluster_masks.py:88-89, "0.18
     for ucf val, 0.14 for ucf train, 0.12 for kin train"): the caller states it; without it the method raises NotImplementedError.
     min_samples=None is the reference's own value for the method: 2 for 'DBSCAN', 3 for 'OPTICS'.
+    method='HDBSCAN' runs HDBSCAN(min_cluster_size=min_cluster_size, min_samples=min_samples, metric='cosine').fit(embeddings).labels_
+    (clustering/hdbscan.py: sklearn's partition, clusters numbered by their smallest row, noise = -1; no radius to state;
+    min_samples=None is min_cluster_size, as in sklearn; l2normalize does not apply; `kernels` is then an HDBSCAN provider).
     process_group: `embeddings` is this rank's row shard (rank order == row order), the returned labels are this rank's.
     exchange: the sharded Lloyd iteration's one collective — 'allreduce' (RCCL through torch.distributed; the default), 'allgather', or
     'oneshot' (the library's one-shot all-to-all over peer-mapped memory, csrc/oneshot.hip); None reads SLIC_KMEANS_EXCHANGE.
@@ -73,6 +77,9 @@ def fit_cluster(embeddings, method='Agglomerative', k=1000, l2normalize=True, fi
         # cluster_masks.py:55-61: DBSCAN(eps=0.14, min_samples=2, metric='cosine', n_jobs=-1).fit(embeddings)
         from .dbscan import DBSCAN
         km = DBSCAN(eps=eps, min_samples=2 if min_samples is None else min_samples, metric='cosine', kernels=kernels).fit(embeddings)
+    elif method == 'HDBSCAN':
+        from .hdbscan import HDBSCAN
+        km = HDBSCAN(min_cluster_size=min_cluster_size, min_samples=min_samples, metric='cosine', kernels=kernels).fit(embeddings)
     elif method == 'OPTICS' and max_eps is not None:
         # cluster_masks.py:88-89: OPTICS(min_samples=3, max_eps=0.20, cluster_method='dbscan', metric='cosine', n_jobs=-1).fit(embeddings)
         from .optics import OPTICS

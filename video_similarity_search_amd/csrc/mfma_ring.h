@@ -28,7 +28,7 @@
 // depth and in what a stage holds — and shares the addressing, the issue, the wait and one stage's MFMAs (slic_rt_compute_stage).
 //
 // Users: km_assign_creg and topk_collect_qreg run the register-operand ring; km_assign_dma and topk_partial_dma the two-operand
-// pieces.  topk_partial_qreg (topk.hip) and db_tiles (dbscan.hip) follow the same contract but still spell the k-tile loop out:
+// pieces.  topk_partial_qreg (topk.hip), db_tiles (dbscan.hip) and hd_tiles (hdbscan.hip) follow the same contract but still spell the k-tile loop out:
 // built on these functions they came out with more SGPRs (SGPR spills in the NK = 8 / 16 instantiations, db_tiles<16, LINK> at
 // 512 VGPRs), so they wait for a form that does not.  The k-means++ distance kernels keep their plain 2-stage loops.
 #pragma once

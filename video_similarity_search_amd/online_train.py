@@ -322,7 +322,7 @@ def _cluster_sharded(cfg):
 def _silhouette_lines(cfg, epoch, embeddings, cluster_labels, kernels):
     """the opt-in label-free score of the cluster step (cfg.ITERCLUSTER.SILHOUETTE): one print, one line in silhouettes.txt"""
     from .clustering.metrics import silhouette_score
-    ignore = -1 if cfg.ITERCLUSTER.METHOD == 'DBSCAN' else None                # DBSCAN's noise rows belong to no cluster
+    ignore = -1 if cfg.ITERCLUSTER.METHOD in ('DBSCAN', 'HDBSCAN') else None    # the noise rows of DBSCAN / HDBSCAN belong to no cluster
     try:
         sil = silhouette_score(embeddings, cluster_labels, metric='cosine', ignore_label=ignore, kernels=kernels)
     except ValueError as e:                     # fewer than 2 clusters, or as many as rows: no score, and no reason to stop training
