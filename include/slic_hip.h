@@ -291,6 +291,7 @@ int slic_kmeanspp_step(const float* X, int64_t N, int D, int ldx, const int32_t*
  * c = 1..K-1: T candidates = searchsorted(cumsum(closest), uniforms[(c-1)*T + t] * current_pot) (clipped), squared distances
  * of every row to them, min with closest, potentials in double, first-minimum candidate kept.  `uniforms` (device,
  * [(K-1)*T] doubles in [0, 1)) are the host RNG's draws — the draws do not depend on the data, so the host never waits.
+ * K == 1 has no draws: uniforms is not read and may be NULL (in slic_kmeanspp_run_batch too).
  * idx_out (device, [K]) receives the chosen row indices. */
 size_t slic_kmeanspp_run_workspace_bytes(int64_t N, int T);
 int slic_kmeanspp_run(const float* X, int64_t N, int D, int ldx, int first, int K, int T, const double* uniforms,

@@ -2193,7 +2193,8 @@ static int kpp_run_all(int64_t N, int R, const int32_t* firsts, int K, int T, co
 // kernel); R * T <= 160.
 extern "C" int slic_kmeanspp_run_batch(const float* Xp, const float* xnorm, int64_t N, int D, int ldx, int R, const int32_t* firsts,
                                        int K, int T, const double* uniforms, int32_t* idx_out, void* workspace, void* stream) {
-  SLIC_REQUIRE(Xp && xnorm && firsts && uniforms && idx_out && workspace, "slic_kmeanspp_run_batch: null pointer");
+  // K == 1: uniforms holds (K - 1) * T = 0 draws and is never read (a caller's empty array may well be a null pointer)
+  SLIC_REQUIRE(Xp && xnorm && firsts && (uniforms || K == 1) && idx_out && workspace, "slic_kmeanspp_run_batch: null pointer");
   SLIC_REQUIRE(N > 0 && K > 0 && K <= N && R >= 1 && T >= 1 && T <= PP_TMAX && R * T <= 160 && D % 8 == 0 && ldx % 4 == 0 &&
                (int64_t)N * ldx * 4 < (1ll << 31), "slic_kmeanspp_run_batch: need 1 <= T <= %d, R * T <= 160, D %% 8 == 0, N * ldx * 4 < 2 GiB", PP_TMAX);
   for (int r = 0; r < R; ++r) SLIC_REQUIRE(firsts[r] >= 0 && firsts[r] < N, "slic_kmeanspp_run_batch: firsts[%d] out of range", r);
@@ -2228,7 +2229,7 @@ extern "C" int slic_kmeanspp_run_batch(const float* Xp, const float* xnorm, int6
 extern "C" int slic_kmeanspp_run(const float* X, int64_t N, int D, int ldx, int first, int K, int T,
                                  const double* uniforms, int32_t* idx_out, const float* Xp, const float* xnorm,
                                  void* workspace, void* stream) {
-  SLIC_REQUIRE(X && uniforms && idx_out && workspace, "slic_kmeanspp_run: null pointer");
+  SLIC_REQUIRE(X && (uniforms || K == 1) && idx_out && workspace, "slic_kmeanspp_run: null pointer");      // K == 1: no draws (slic_kmeanspp_run_batch)
   SLIC_REQUIRE(N > 0 && K > 0 && K <= N && first >= 0 && first < N && T >= 1 && T <= PP_TMAX && D % 4 == 0 && ldx % 4 == 0 &&
                (size_t)T * D * 4 <= 48 * 1024, "slic_kmeanspp_run: need 1 <= T <= %d, D %% 4 == 0, T*D*4 <= 48 KiB", PP_TMAX);
   if (Xp && xnorm && D % 8 == 0 && (int64_t)N * ldx * 4 < (1ll << 31))
