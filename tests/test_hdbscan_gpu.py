@@ -124,6 +124,8 @@ def _check_round(dev, W, comp, C, b):
 
 
 CASES = [(N, D, ms) for N in (2, 127, 129, 300, 1000) for D in (3, 32, 40, 512) for ms in (1, 2, 5) if ms <= N]
+# hd_tiles<NK> holds a row in NK = 4 ceil(Dp / 128) k-tiles: the D above reach NK = 4 and 16, these NK = 8 and 12
+CASES += [(N, D, ms) for N in (129, 300) for D in (200, 320) for ms in (2, 5)]
 
 
 @pytest.mark.parametrize("N,D,ms", CASES)

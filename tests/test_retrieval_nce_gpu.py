@@ -72,9 +72,10 @@ def test_self_retrieval_and_distance_matrix(gpu, golden_dir):
 
 # every partial kernel of csrc/topk.hip: query operand in registers with 4 / 8 / 16 k-tiles (D <= 128 / 256 / 512), the
 # 2-stage ring for D > 512, the short pending columns of a large k, several gallery slices with a ragged last one
+# (k = 88 leaves 2 or 3 pending slots per lane: topk_partial_qreg<NK, 2, ..>, here with NK = 4, 8 and 16)
 @pytest.mark.parametrize("Nq,Ng,D,k", [(1, 50, 8, 50), (129, 1000, 128, 1), (1000, 20000, 512, 20), (33, 257, 40, 7),
                                        (200, 3001, 256, 50), (300, 40000, 200, 50), (64, 2000, 640, 10),
-                                       (100, 5000, 512, 88), (130, 700, 1024, 3)])
+                                       (100, 5000, 512, 88), (130, 700, 1024, 3), (33, 257, 40, 88), (33, 300, 136, 88)])
 def test_topk_shapes_vs_oracle(gpu, Nq, Ng, D, k):
     from oracle import retrieval as orr
     from video_similarity_search_amd.evaluate import cosine_topk

@@ -57,9 +57,10 @@ def _collect_env(v):
 
 # the cosine tests' shape list: every partial-kernel instantiation (query operand in registers with 4 / 8 / 16 k-tiles, the 2-stage
 # ring for D > 512, short pending columns at large k, ragged last slices), a zero gallery row
+# (k = 88 leaves 2 or 3 pending slots per lane: topk_partial_qreg<NK, 2, ..>, here with NK = 4, 8 and 16)
 @pytest.mark.parametrize("Nq,Ng,D,k", [(1, 50, 8, 50), (129, 1000, 128, 1), (1000, 20000, 512, 20), (33, 257, 40, 7),
                                        (200, 3001, 256, 50), (300, 40000, 200, 50), (64, 2000, 640, 10),
-                                       (100, 5000, 512, 88), (130, 700, 1024, 3)])
+                                       (100, 5000, 512, 88), (130, 700, 1024, 3), (33, 257, 40, 88), (33, 300, 136, 88)])
 def test_euclidean_topk_shapes_vs_oracle(gpu, Nq, Ng, D, k):
     from video_similarity_search_amd.evaluate import euclidean_topk
     rng = np.random.default_rng(Nq + Ng + 1)

@@ -62,23 +62,6 @@ __device__ int db_unite(int* parent, int a, int b) {
   }
 }
 
-// prep: one wave per row
-__global__ __launch_bounds__(256) void db_prep(const float* __restrict__ X, int N, int ldx, int D, int Dp, double* __restrict__ inv,
-                                               float* __restrict__ Xn) {
-  const int lane = threadIdx.x & 63;
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= N) return;
-  const float* x = X + (int64_t)row * ldx;
-  double s = 0.0;
-  for (int k = lane; k < D; k += 64) s = fma((double)x[k], (double)x[k], s);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-  const double iv = s > 0.0 ? 1.0 / sqrt(s) : 0.0;
-  if (lane == 0) inv[row] = iv;
-  float* xn = Xn + (int64_t)row * Dp;
-  for (int k = lane; k < Dp; k += 64) xn[k] = k < D ? (float)((double)x[k] * iv) : 0.f;
-}
-
 struct DbArgs {
   const float* Xcb;          // [N, Dp]: Xn for the count pass, [Xc; Xb] for the others
   int Dp;
@@ -98,9 +81,9 @@ template <int NK, int MODE>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void db_tiles(DbArgs p) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   static_assert(NK % 4 == 0, "a gallery tile is a whole number of ring turns");
-  constexpr int STAGE_FLOATS = DB_B * SLIC_RT_BK;
+  static_assert(DB_B * SLIC_RT_BK == SLIC_RT_TILE, "a ring stage is one DB_B-row tile");
   constexpr bool TRI = MODE != DB_BORDER;
-  int* pend = (int*)(lds + 4 * STAGE_FLOATS);                  // [4 waves][DB_PC][64] gallery rows, one column per lane
+  int* pend = (int*)(lds + 4 * SLIC_RT_TILE);                  // [4 waves][DB_PC][64] gallery rows, one column per lane
   int* groot = pend + 4 * DB_PC * 64;                          // [128] cached roots of the gallery tile
   int* tl = groot + DB_B;                                      // [DB_SLICE] gallery tiles this workgroup computes
   int* sm = tl + DB_SLICE;                                     // [2] root min / max of a tile (link skip)
@@ -152,34 +135,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   const int q = I * DB_B + 32 * wave + r;
   const bool qvalid = q < nA;
   f32x4 qr[NK][4];
-  {
-    const float* qrow = A + (int64_t)(qvalid ? q : nA - 1) * Dp;
-#pragma unroll
-    for (int kt = 0; kt < NK; ++kt)
-#pragma unroll
-      for (int qd = 0; qd < 4; ++qd) {
-        const int c = 32 * kt + 8 * qd + 4 * h;
-        f32x4 z = {0.f, 0.f, 0.f, 0.f};
-        qr[kt][qd] = c < Dp ? *(const f32x4*)(qrow + c) : z;     // Dp % 8 == 0: a chunk is inside the row or past it
-      }
-  }
-  const int srow = tid >> 3;
-  const int cq = (tid & 7) ^ ((srow >> 1) & 7);              // SOURCE chunk of this lane (LDS slot = tid & 7)
+  slic_rt_load_frags<NK>(qr, A + (int64_t)(qvalid ? q : nA - 1) * Dp, Dp, h);
+  const SlicRtLane ln = slic_rt_lane(tid, Dp);
   const __amdgpu_buffer_rsrc_t rs_g = __builtin_amdgcn_make_buffer_rsrc((void*)B, 0, (int)((int64_t)nB * Dp * 4), 0x00020000);
-  constexpr unsigned OOB = 0xFFFFFF00u;
   unsigned goff[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) goff[i] = ((unsigned)(srow + 32 * i) * (unsigned)Dp + cq * 4) * 4u;
-  const int klim = Dp - cq * 4;
+  slic_rt_offsets<4>(goff, ln, (unsigned)Dp * 4u);
+  // ring step (tile, kt) into `stage`; a tile past the list and a k-tile past Dp come from out of range: zeros
   auto issue = [&](int tile, int kt, int stage) {
-    float* Gs = lds + stage * STAGE_FLOATS;
-    const bool kin = kt * SLIC_RT_BK < klim && tile < ntl;
-    const unsigned kb = (unsigned)kt * (SLIC_RT_BK * 4u);
     const unsigned gb = tile < ntl ? (unsigned)tl[tile] * (unsigned)(DB_B * Dp * 4) : 0u;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_g, (__attribute__((address_space(3))) void*)(Gs + (8 * wave + 32 * i) * SLIC_RT_BK),
-                                               16, (int)(kin ? gb + goff[i] + kb : OOB), 0, 0, 0);
+    slic_rt_issue(rs_g, lds + stage * SLIC_RT_TILE, wave, goff, gb, kt, ln.kin(kt) && tile < ntl);
   };
 
   const float hi = p.hi, lo = p.lo;
@@ -216,9 +180,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   f32x4 a[2][4];
   int gfirst = 0;                                              // link / border: first-level parent of this thread's gallery row
   issue(0, 0, 0);
-  issue(NK > 1 ? 0 : 1, NK > 1 ? 1 : 0, 1);
-  issue(NK > 2 ? 0 : 1, NK > 2 ? 2 : 0, 2);
-  asm volatile("s_waitcnt vmcnt(8)" ::: "memory");             // step 0 has landed
+  issue(0, 1, 1);
+  issue(0, 2, 2);
+  slic_rt_wait<8>();                                           // step 0 has landed
   __builtin_amdgcn_s_barrier();
 #pragma unroll
   for (int ct = 0; ct < 4; ++ct) a[0][ct] = *(const f32x4*)&lds[slic_rt_off(32 * ct + r, h)];
@@ -231,7 +195,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
       for (int v = 0; v < 16; ++v) acc[ct][v] = 0.f;
 #pragma unroll
     for (int kt = 0; kt < NK; ++kt) {
-      asm volatile("s_waitcnt vmcnt(4)" ::: "memory");         // step s + 1 has landed (this wave's part of it)
+      slic_rt_wait<4>();                                       // step s + 1 has landed (this wave's part of it)
       __builtin_amdgcn_s_barrier();                            // ... everybody's; and stage (kt + 3) & 3 has been read by all
       {
         const int kn = kt + 3;
@@ -248,25 +212,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
           if (tid < DB_B) groot[tid] = gfirst;
         }
       }
-      const float* Gs = lds + (kt & 3) * STAGE_FLOATS;
-      const float* Gn = lds + ((kt + 1) & 3) * STAGE_FLOATS;
-      __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-      for (int qd = 0; qd < 4; ++qd) {
-        const int cur = qd & 1, nxt = cur ^ 1;
-#pragma unroll
-        for (int ct = 0; ct < 4; ++ct)
-          a[nxt][ct] = qd < 3 ? *(const f32x4*)&Gs[slic_rt_off(32 * ct + r, 2 * (qd + 1) + h)]
-                              : *(const f32x4*)&Gn[slic_rt_off(32 * ct + r, h)];       // first fragments of the next step
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-          for (int ct = 0; ct < 4; ++ct)
-            acc[ct] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[cur][ct][t], qr[kt][qd][t], acc[ct], 0, 0, 0);
-        __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
-        __builtin_amdgcn_sched_group_barrier(0x008, 16, 0);
-      }
-      __builtin_amdgcn_s_setprio(0);
+      slic_rt_ktile_mfma<false, 4>(acc, a, qr[kt], lds, kt & 3, r, h);
     }
     // ---- epilogue: lane (r, h) holds query q against gallery rows g0 + ct * 32 + (v & 3) + 8 (v >> 2) + 4 h
     const bool diag = TRI && J == I;
@@ -330,7 +276,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     const int b = min(best, __shfl_xor(best, 32));
     if (h == 0 && qvalid && b != INT_MAX) atomicMin(&p.best[q], b);
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");             // the trailing all-zero DMAs must land before the workgroup leaves
+  slic_rt_wait<0>();                                           // the trailing all-zero DMAs must land before the workgroup leaves
 }
 
 // core flags, labels = -1, and the two compactions (core rows, border candidates) in row order
@@ -496,7 +442,7 @@ int db_label_passes(const float* X, int n, int ldx, int D, double eps, int min_s
   SLIC_HIP_CHECK(hipMemcpyAsync(L.meta, &n, sizeof(int), hipMemcpyHostToDevice, st));
   SLIC_HIP_CHECK(hipMemsetAsync(cnt, 0, (size_t)n * sizeof(int), st));
   { int r = db_mark(st, ev, 0); if (r) return r; }
-  db_prep<<<(n + 3) / 4, 256, 0, st>>>(X, n, ldx, D, Dp, L.inv, L.Xn);
+  db_prep<0><<<(n + 3) / 4, 256, 0, st>>>(X, n, ldx, D, Dp, L.inv, L.Xn);
   SLIC_LAUNCH_CHECK();
   { int r = db_mark(st, ev, 1); if (r) return r; }
 

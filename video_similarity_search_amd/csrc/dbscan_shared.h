@@ -1,6 +1,6 @@
 // What csrc/optics.hip shares with csrc/dbscan.hip: the float64 pair decision, the size of the one-workgroup scans (slic_wg_scan,
 // wg_scan.h), the workspace layout of the label passes and the passes themselves (db_label_passes: prep, count, compact, link, number,
-// border).  The kernels stay in dbscan.hip.
+// border); and with csrc/hdbscan.hip the unit-row preparation (db_prep).  The other kernels stay in dbscan.hip.
 #pragma once
 #include "wg_scan.h"
 #include <math.h>
@@ -20,6 +20,26 @@ __device__ inline bool db_exact(const float* __restrict__ X, int ldx, int D, con
   double d = 1.0 - s * inv[a] * inv[b];
   d = fmin(fmax(d, 0.0), 2.0);
   return d <= eps;
+}
+
+// prep of dbscan.hip and hdbscan.hip, one wave per row: inv[i] = 1 / ||x_i|| in float64 (0 for a zero row), Xn[i] = fp32(x_i * inv[i]),
+// zero-padded to Dp columns.  The summation order and the rounding are part of both contracts.  A template: the library is built
+// without relocatable device code, so every object that launches it compiles its own copy, and one that does not (optics.o) has none.
+template <int = 0>
+__global__ __launch_bounds__(256) void db_prep(const float* __restrict__ X, int N, int ldx, int D, int Dp, double* __restrict__ inv,
+                                               float* __restrict__ Xn) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= N) return;
+  const float* x = X + (int64_t)row * ldx;
+  double s = 0.0;
+  for (int k = lane; k < D; k += 64) s = fma((double)x[k], (double)x[k], s);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+  const double iv = s > 0.0 ? 1.0 / sqrt(s) : 0.0;
+  if (lane == 0) inv[row] = iv;
+  float* xn = Xn + (int64_t)row * Dp;
+  for (int k = lane; k < Dp; k += 64) xn[k] = k < D ? (float)((double)x[k] * iv) : 0.f;
 }
 
 struct DbLayout {

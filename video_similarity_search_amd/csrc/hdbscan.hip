@@ -30,23 +30,6 @@
 
 typedef unsigned long long u64;
 
-// prep: one wave per row
-__global__ __launch_bounds__(256) void hd_prep(const float* __restrict__ X, int N, int ldx, int D, int Dp, double* __restrict__ inv,
-                                               float* __restrict__ Xn) {
-  const int lane = threadIdx.x & 63;
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= N) return;
-  const float* x = X + (int64_t)row * ldx;
-  double s = 0.0;
-  for (int k = lane; k < D; k += 64) s = fma((double)x[k], (double)x[k], s);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-  const double iv = s > 0.0 ? 1.0 / sqrt(s) : 0.0;
-  if (lane == 0) inv[row] = iv;
-  float* xn = Xn + (int64_t)row * Dp;
-  for (int k = lane; k < Dp; k += 64) xn[k] = k < D ? (float)((double)x[k] * iv) : 0.f;
-}
-
 // d of rule 1 in float64 for one pair, by one wave: lane l takes elements l, l + 64, ... of the raw rows (lower row first) by fma, then
 // an xor butterfly; every lane returns the value.  The order is fixed and the same from either end of the pair.
 __device__ __forceinline__ double hd_d64(const float* __restrict__ X, int ldx, int D, const double* __restrict__ inv, int i, int j, int lane) {
@@ -168,25 +151,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
       } else if (kt == 2) {
         if (tid < DB_B) { gcore[tid] = ncore; gcomp[tid] = ncomp; }
       }
-      const float* Gs = lds + (kt & 3) * SLIC_RT_TILE;
-      const float* Gn = lds + ((kt + 1) & 3) * SLIC_RT_TILE;
-      __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-      for (int qd = 0; qd < 4; ++qd) {
-        const int cur = qd & 1, nxt = cur ^ 1;
-#pragma unroll
-        for (int ct = 0; ct < 4; ++ct)
-          a[nxt][ct] = qd < 3 ? *(const f32x4*)&Gs[slic_rt_off(32 * ct + r, 2 * (qd + 1) + h)]
-                              : *(const f32x4*)&Gn[slic_rt_off(32 * ct + r, h)];       // first fragments of the next step
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-          for (int ct = 0; ct < 4; ++ct)
-            acc[ct] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[cur][ct][t], qr[kt][qd][t], acc[ct], 0, 0, 0);
-        __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
-        __builtin_amdgcn_sched_group_barrier(0x008, 16, 0);
-      }
-      __builtin_amdgcn_s_setprio(0);
+      slic_rt_ktile_mfma<false, 4>(acc, a, qr[kt], lds, kt & 3, r, h);
     }
     // ---- epilogue: lane (r, h) holds query q against gallery rows g0 + ct * 32 + (v & 3) + 8 (v >> 2) + 4 h, ascending in (ct, v).
     // A row past N has core = +inf: its w is never < bw.  A zero row scores 0 against everything: d = 1 (rule 1).
@@ -323,7 +288,7 @@ extern "C" int slic_hdbscan_core(const float* X, int64_t N, int ldx, int D, int 
   if (hd_last.timed) SLIC_HIP_CHECK(hipEventRecord(hd_ev[HD_EV_CORE0], st));
   const int meta[3] = {n, D, min_samples};
   SLIC_HIP_CHECK(hipMemcpyAsync(L.meta, meta, sizeof(meta), hipMemcpyHostToDevice, st));
-  hd_prep<<<(n + 3) / 4, 256, 0, st>>>(X, n, ldx, D, Dp, L.inv, L.Xn);
+  db_prep<0><<<(n + 3) / 4, 256, 0, st>>>(X, n, ldx, D, Dp, L.inv, L.Xn);
   SLIC_LAUNCH_CHECK();
   { int r = slic_cosine_topk(L.Xn, n, L.Xn, n, Dp, k, 0, L.knn, L.knn_dist, L.topk_ws, stream); if (r) return r; }
   hd_core<<<(n + 3) / 4, 256, 0, st>>>(X, n, ldx, D, L.inv, L.knn, k, core_dist, L.core32);

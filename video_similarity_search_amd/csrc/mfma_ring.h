@@ -27,10 +27,25 @@
 // The two-operand ring (both tiles by DMA; km_assign_dma, topk_partial_dma) keeps its loop in the kernel — the kernels differ in
 // depth and in what a stage holds — and shares the addressing, the issue, the wait and one stage's MFMAs (slic_rt_compute_stage).
 //
-// Users: km_assign_creg and topk_collect_qreg run the register-operand ring; km_assign_dma and topk_partial_dma the two-operand
-// pieces.  topk_partial_qreg (topk.hip), db_tiles (dbscan.hip) and hd_tiles (hdbscan.hip) follow the same contract but still spell the k-tile loop out:
-// built on these functions they came out with more SGPRs (SGPR spills in the NK = 8 / 16 instantiations, db_tiles<16, LINK> at
-// 512 VGPRs), so they wait for a form that does not.  The k-means++ distance kernels keep their plain 2-stage loops.
+// Users.  km_assign_creg (kmeans.hip), topk_collect_qreg (topk.hip) and moco_ring (moco.hip) run the whole register-operand ring:
+// slic_rt_ring_prime, then slic_rt_ring_ktile per k-tile with their issue and between-work as lambdas.  km_assign_dma and
+// topk_partial_dma run the two-operand pieces.  db_tiles (dbscan.hip), hd_tiles (hdbscan.hip) and topk_collect_bf16 (topk_bf16.h)
+// follow the same contract but keep the k-tile loop — wait, barrier, issue, between-work — in the kernel and share the step's MFMA
+// block, slic_rt_ktile_mfma, besides the prologue pieces (slic_rt_load_frags, slic_rt_lane, slic_rt_offsets, slic_rt_issue,
+// slic_rt_wait): handed to slic_rt_ring_ktile as lambdas, that work cost db_tiles two SGPRs in every instantiation and
+// db_tiles<16, LINK> an SGPR spill at 512 VGPRs; with the loop left in place their register counts, LDS and scratch are the
+// hand-written loop's.  km_assign_bf16 (kmeans_bf16.h) takes the prologue pieces and spells the MFMA block out; topk_partial_qreg
+// (topk.hip) spells out both.  Calling slic_rt_ktile_mfma gives every topk_partial_qreg two more SGPRs (more SGPR spills at
+// NK = 8 / 16) and km_assign_bf16<8> four more SGPR spills; topk_partial_qreg's prologue on the helpers kept its register
+// counts but measured 0.15 - 0.3 % slower in the streaming search at D = 512, so the kernel stays as it was.
+// The cause of the SGPRs: a force-inlined callee is optimised on its own first, so it arrives in
+// the kernel with its qd loop unrolled and every frag[][] index constant, while the kernel's own loops are still rolled; the
+// target's alloca-to-vector promotion, which runs right after inlining and takes arrays of up to 32 registers, then turns the
+// 32-float frag[2][4] into ONE 32-register value that the tile loop carries whole.  Written in place, frag is indexed by the still
+// rolled qd loop at that point, is left alone, and falls apart into eight 4-register values after unrolling.  The optimised IR
+// of the two forms of topk_partial_qreg differs in nothing else (profiles/mfma_ktile_device_code_diff.txt); the three kernels
+// that call the block get the same wide value and have the registers to spare.
+// The k-means++ distance kernels keep their plain 2-stage loops.
 #pragma once
 #include "common.h"
 
@@ -114,11 +129,53 @@ __device__ __forceinline__ void slic_rt_ring_prime(f32x4 (&frag)[2][4], const fl
   for (int i = 0; i < 4; ++i) frag[0][i] = *(const f32x4*)&lds[slic_rt_off(32 * i + r, h)];
 }
 
+// Register-operand ring: the MFMA block of one ring step, shared by slic_rt_ring_ktile and by the kernels that keep their own k-tile
+// loop (their wait, barrier, issue and between-work stay in the kernel, in front of this call).  regop: this k-tile's sixteen operand
+// registers; st: the stage the step computes from.  The next stage was published by this step's barrier: the last quarter fetches
+// the next step's first fragments from it, and `frag` carries them across calls.  REG_A: the register operand is MFMA operand A
+// (else B); NACC: accumulators in use (a ragged last tile has fewer; all four fragments are still fetched: the step after a tile's
+// last belongs to a full tile).  BF16: a fragment is 8 bf16 values and feeds one v_mfma_f32_32x32x16_bf16 instead of four
+// v_mfma_f32_32x32x2_f32.  k order inside every accumulator: qd ascending, t ascending, lane half 0 then 1.
+// (The ring's base and a stage number, not two stage pointers: handed `lds + constant` the compiler indexes each stage by a float
+// offset of its own instead of the loop's one lane address plus immediates, and every user's device code moves.)
+template <bool REG_A, int NACC, bool BF16 = false>
+__device__ __forceinline__ void slic_rt_ktile_mfma(f32x16 (&acc)[4], f32x4 (&frag)[2][4], const f32x4 (&regop)[4], const float* lds,
+                                                   int st, int r, int h) {
+  typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+  const float* Ts = lds + st * SLIC_RT_TILE;
+  const float* Tn = lds + ((st + 1) & 3) * SLIC_RT_TILE;
+  __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+  for (int qd = 0; qd < 4; ++qd) {
+    const int cur = qd & 1, nxt = cur ^ 1;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      frag[nxt][i] = qd < 3 ? *(const f32x4*)&Ts[slic_rt_off(32 * i + r, 2 * (qd + 1) + h)]
+                            : *(const f32x4*)&Tn[slic_rt_off(32 * i + r, h)];     // first fragments of the next step
+    if constexpr (BF16) {
+#pragma unroll
+      for (int i = 0; i < NACC; ++i) {
+        const bf16x8 f = __builtin_bit_cast(bf16x8, frag[cur][i]), g = __builtin_bit_cast(bf16x8, regop[qd]);
+        acc[i] = REG_A ? __builtin_amdgcn_mfma_f32_32x32x16_bf16(g, f, acc[i], 0, 0, 0)
+                       : __builtin_amdgcn_mfma_f32_32x32x16_bf16(f, g, acc[i], 0, 0, 0);
+      }
+    } else {
+#pragma unroll
+      for (int t = 0; t < 4; ++t)
+#pragma unroll
+        for (int i = 0; i < NACC; ++i)
+          acc[i] = REG_A ? __builtin_amdgcn_mfma_f32_32x32x2f32(regop[qd][t], frag[cur][i][t], acc[i], 0, 0, 0)
+                         : __builtin_amdgcn_mfma_f32_32x32x2f32(frag[cur][i][t], regop[qd][t], acc[i], 0, 0, 0);
+    }
+    __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
+    __builtin_amdgcn_sched_group_barrier(0x008, BF16 ? NACC : 4 * NACC, 0);
+  }
+  __builtin_amdgcn_s_setprio(0);
+}
+
 // Register-operand ring, k-tile kt of a tile (call it for kt = 0 .. NK - 1, unrolled: kt is a constant after inlining).
 // issue(kn) issues ring step kn of the CURRENT tile, kn >= NK meaning step kn - NK of the next one; between(kt) is the kernel's own
-// work of this k-tile, ahead of the MFMAs.  REG_A: the register operand is MFMA operand A (else B); NACC: accumulators in use
-// (a ragged last tile has fewer; all four fragments are still fetched: the step after a tile's last belongs to a full tile).
-// k order inside every accumulator: qd ascending, t ascending, lane half 0 then 1.
+// work of this k-tile, ahead of the MFMAs.  REG_A, NACC: as in slic_rt_ktile_mfma, which does the step's MFMAs.
 template <int ST, bool REG_A, int NACC, bool LGKM, int NK, typename Issue, typename Between>
 __device__ __forceinline__ void slic_rt_ring_ktile(int kt, f32x16 (&acc)[4], f32x4 (&frag)[2][4], const f32x4 (&regop)[NK][4],
                                                    const float* lds, int r, int h, const Issue& issue, const Between& between) {
@@ -128,26 +185,7 @@ __device__ __forceinline__ void slic_rt_ring_ktile(int kt, f32x16 (&acc)[4], f32
   __builtin_amdgcn_s_barrier();                                // ... everybody's; and stage (kt + ST - 1) % ST has been read by all
   issue(kt + ST - 1);
   between(kt);
-  const float* Ts = lds + (kt % ST) * SLIC_RT_TILE;
-  const float* Tn = lds + ((kt + 1) % ST) * SLIC_RT_TILE;
-  __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-  for (int qd = 0; qd < 4; ++qd) {
-    const int cur = qd & 1, nxt = cur ^ 1;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-      frag[nxt][i] = qd < 3 ? *(const f32x4*)&Ts[slic_rt_off(32 * i + r, 2 * (qd + 1) + h)]
-                            : *(const f32x4*)&Tn[slic_rt_off(32 * i + r, h)];     // first fragments of the next step
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-      for (int i = 0; i < NACC; ++i)
-        acc[i] = REG_A ? __builtin_amdgcn_mfma_f32_32x32x2f32(regop[kt][qd][t], frag[cur][i][t], acc[i], 0, 0, 0)
-                       : __builtin_amdgcn_mfma_f32_32x32x2f32(frag[cur][i][t], regop[kt][qd][t], acc[i], 0, 0, 0);
-    __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
-    __builtin_amdgcn_sched_group_barrier(0x008, 4 * NACC, 0);
-  }
-  __builtin_amdgcn_s_setprio(0);
+  slic_rt_ktile_mfma<REG_A, NACC>(acc, frag, regop[kt], lds, kt % ST, r, h);
 }
 
 // Two-operand ring: the MFMAs of one stage.  Bs / As: the stage's B and A operand tiles; the wave multiplies rows rowB + r of Bs

@@ -83,24 +83,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
       slic_rt_wait<4>();
       __builtin_amdgcn_s_barrier();
       issue(kt + 3 >= NK ? tile + 1 : tile, kt + 3 >= NK ? kt + 3 - NK : kt + 3);
-      const float* Ts = lds + (kt & 3) * SLIC_RT_TILE;
-      const float* Tn = lds + ((kt + 1) & 3) * SLIC_RT_TILE;
-      __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-      for (int qd = 0; qd < 4; ++qd) {
-        const int cur = qd & 1, nxt = cur ^ 1;
-#pragma unroll
-        for (int ct = 0; ct < 4; ++ct)
-          a[nxt][ct] = qd < 3 ? *(const f32x4*)&Ts[slic_rt_off(32 * ct + r, 2 * (qd + 1) + h)]
-                              : *(const f32x4*)&Tn[slic_rt_off(32 * ct + r, h)];       // first fragments of the next step
-#pragma unroll
-        for (int ct = 0; ct < 4; ++ct)
-          acc[ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(tkb_bf16x8, a[cur][ct]),
-                                                            __builtin_bit_cast(tkb_bf16x8, qr[kt][qd]), acc[ct], 0, 0, 0);
-        __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
-        __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
-      }
-      __builtin_amdgcn_s_setprio(0);
+      slic_rt_ktile_mfma<false, 4, true>(acc, a, qr[kt], lds, kt & 3, r, h);
     }
     const int g0 = gbeg + tile * TK_BG;
     const bool ragged = g0 + TK_BG > gend;
