@@ -1155,6 +1155,50 @@ int slic_tsne_step(const float* P, int64_t N, float exaggeration, float momentum
 int slic_tsne_gram(const float* X, int64_t N, int D, int64_t ldx, const double* mean, int shares, double* partial, double* G,
                    void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * k-NN classification and ranked retrieval metrics on the top-k lists (csrc/knn.hip).
+ * ------------------------------------------------------------------------------------------
+ * Both calls read [Nq, k] tables as slic_cosine_topk / slic_euclidean_topk / slic_topk_merge_lists write them: int32 gallery rows,
+ * distances ascending with ties to the lower row, entries < 0 or >= Ng are padding.  1 <= k <= SLIC_KNN_MAX_K.  Neither takes a
+ * workspace, neither synchronises, neither uses a floating-point atomic: the results are a function of the tables alone.
+ *
+ * slic_knn_vote: the weighted vote of sklearn's KNeighborsClassifier / the k-NN monitor.  g_labels [Ng] int64 are classes 0 .. C - 1,
+ * 1 <= C <= SLIC_KNN_MAX_CLASSES.  An entry VOTES unless it is padding or its gallery label is < 0 (noise used as a pseudo-label) or
+ * >= C.  With d_j the table's distance of the voting entry at rank j, its weight w_j is
+ *   SLIC_KNN_UNIFORM   1                                      (dist may be NULL)
+ *   SLIC_KNN_DISTANCE  1 / d_j; if any voting entry of the row has d == 0: (d_j == 0)                     (sklearn's rule)
+ *   SLIC_KNN_SOFTMAX   expf((d_first - d_j) * (1 / temperature)), d_first = the distance of the row's first voting entry: every
+ *                      weight is <= 1; for cosine distances this is exp(sim_j / T) up to a factor the normalisation removes.
+ * s[c] = the float32 sum of the w_j with label c, added one at a time in rank order from 0; tot = the sum of s over the classes: lane l
+ * of 64 adds s[l], s[l + 64], ... in that order, then t += t[lane ^ o] for o = 32, 16, .. 1.  Outputs, each may be NULL:
+ *   proba [Nq, C]      s[c] / tot
+ *   pred  [Nq, n_top]  the n_top classes by (s descending, class ascending) — the lowest class wins a tie, as numpy's argmax does;
+ *                      classes nobody voted for take part with s = 0; -1 past the C-th place
+ *   score [Nq, n_top]  their s (0 where pred is -1)
+ * n_top <= SLIC_KNN_MAX_TOP, 0 exactly when pred and score are both NULL.  A row without a voting entry gets proba = 0, pred = -1,
+ * score = 0.  SLIC_EINVAL for sizes outside the limits, an unknown mode, dist == NULL in a mode that weighs, temperature <= 0.
+ *
+ * slic_retrieval_ranked: with h_j = (g_labels[idx[q, j]] == q_labels[q]) (padding never hits) and c_j = h_0 + .. + h_j, for each of
+ * the n_ks <= SLIC_KNN_MAX_CUTS ascending cut-offs K (a HOST array, 1 <= K <= k) and n_rel[q] = how many gallery rows are relevant:
+ *   P@K = c_{K-1} / K,  R@K = c_{K-1} / n_rel,  AP@K = (sum_{j < K, h_j} c_j / (j + 1)) / min(n_rel, K),  RR = 1 / (first hit + 1)
+ * in double; R and AP are 0 for n_rel <= 0, RR is 0 without a hit in the k entries.  per_query [Nq, n_ks, 3] = (P, R, AP), rr [Nq].
+ * record (may be NULL; 3 * n_ks + 2 doubles): the means of the 3 * n_ks columns in per_query's order, the mean of rr, and the number
+ * of queries with n_rel > 0.  P and RR average over all Nq queries, R and AP over those with n_rel > 0 (0 when there is none).  A
+ * second launch adds each column in double in a fixed order (thread t of 256: queries t, t + 256, ... ascending; then slic_wg_fold's
+ * halving). */
+#define SLIC_KNN_MAX_K 1024
+#define SLIC_KNN_MAX_CLASSES 4096
+#define SLIC_KNN_MAX_TOP 8
+#define SLIC_KNN_MAX_CUTS 8
+#define SLIC_KNN_UNIFORM 0
+#define SLIC_KNN_DISTANCE 1
+#define SLIC_KNN_SOFTMAX 2
+int slic_knn_vote(const int32_t* idx, const float* dist, int Nq, int k, const int64_t* g_labels, int Ng, int C, int mode,
+                  float temperature, int n_top, float* proba, int32_t* pred, float* score, void* stream);
+int slic_retrieval_ranked(const int32_t* idx, int Nq, int k, const int64_t* q_labels, const int64_t* g_labels, int Ng,
+                          const int32_t* n_rel, const int32_t* cutoffs, int n_ks, double* per_query, double* rr, double* record,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif

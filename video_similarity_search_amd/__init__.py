@@ -16,6 +16,8 @@ path behind the reference's Python call surface (rvl-lab-utoronto/video_similari
     misc.distributed_helper                 <- misc/distributed_helper.py
     tsne.tsne_projection, manifold.TSNE, decomposition.PCA
                                             <- tsne.py (the data path: class subset, PCA(50), exact t-SNE; no plotting)
+    neighbors.KNeighborsClassifier / NearestNeighbors, evaluate.knn_classify / retrieval_metrics
+                                            (not in the reference: sklearn.neighbors' names on the device top-k lists)
 
 All arithmetic runs in hand-written HIP kernels in csrc/ behind the C ABI of include/slic_hip.h
 (libslic_hip.so, loaded with ctypes).  There is no CPU fallback: importing a compute entry point
@@ -23,7 +25,8 @@ without the built library, or calling it without a gfx950 device, raises.
 """
 __version__ = "0.1.0"
 
-_EXPORTS = {"TSNE": "manifold", "PCA": "decomposition", "tsne_projection": "tsne"}
+_EXPORTS = {"TSNE": "manifold", "PCA": "decomposition", "tsne_projection": "tsne", "KNeighborsClassifier": "neighbors",
+            "NearestNeighbors": "neighbors"}
 
 
 def __getattr__(name):

@@ -226,6 +226,9 @@ SIGNATURES = {
     "slic_tsne_symmetrize": (I, [P, L, P, P]),
     "slic_tsne_step": (I, [P, L, F, F, F, I, P, P, P, P, P, P, P]),
     "slic_tsne_gram": (I, [P, L, I, L, P, I, P, P, P]),
+    # k-NN vote and ranked retrieval metrics on the top-k lists
+    "slic_knn_vote": (I, [P, P, I, I, P, I, I, I, F, I, P, P, P, P]),
+    "slic_retrieval_ranked": (I, [P, I, I, P, P, I, P, P, I, P, P, P, P]),
 }
 
 

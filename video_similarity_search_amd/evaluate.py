@@ -9,13 +9,17 @@ iic_retrieve_clips.py that sit on the hot path:
     k_nearest_embeddings(args, model, ..., plot=False)    <- evaluate.py:353-400
     evaluate(model, data_loader, ...) / get_embeddings_and_labels(...)   <- evaluate.py:146-205, 310-350
     topk_retrieval(args | arrays)                          <- iic_retrieve_clips.py:275-314
+    knn_classify(x, x_labels, y, y_labels, k, weights)     (not in the reference: weighted k-NN classification accuracy on the top-k lists)
+    retrieval_metrics(x, x_labels, y, y_labels, ks)        (not in the reference: precision@k, recall@k, mAP@k, MRR on the top-k lists)
 
 The reference computes an N_q x N_g sklearn cosine_distances matrix on the host and argsorts every row.
 Here the matrix (when a caller really wants it) comes from the fp32-MFMA gather-GEMM with a
 (1 - s, clamp at 0) epilogue, and the top-k paths never build it: `cosine_topk` fuses the similarity GEMM
 with a per-query streaming top-k (csrc/topk.hip); `euclidean_topk` runs the same kernels on q.g - |g|^2 / 2 and
 recomputes the winners' distances directly (LOSS.DIST_METRIC 'euclidean').  Plot/heat-map helpers of evaluate.py
-are out of scope.
+are out of scope.  knn_classify / retrieval_metrics consume the [Nq, k] tables where the search leaves them (csrc/knn.hip:
+slic_knn_vote, slic_retrieval_ranked; classes with sklearn's names in neighbors.py); k_nearest_embeddings runs the k-NN monitor from its
+one search when cfg.VAL.KNN_K > 0 and is otherwise unchanged.
 """
 import ctypes
 import functools
@@ -290,6 +294,134 @@ def topk_acc_device(x_embeddings, x_labels, y_embeddings=None, y_labels=None, to
     return hits.cpu().numpy().astype(np.float64) / idx.shape[0]
 
 
+def _knn_provider(kernels):
+    from .neighbors import HipKnnKernels
+    return HipKnnKernels() if kernels is None else kernels       # raises SlicError without a gfx950 device
+
+
+def _class_count(labels, num_classes):
+    """the C of the vote: num_classes, or max label + 1 (host labels: no device work; a device tensor costs one read-back)"""
+    if num_classes is None:
+        if torch.is_tensor(labels):
+            num_classes = int(labels.max()) + 1 if labels.numel() else 1
+        else:
+            a = np.asarray(labels)
+            num_classes = int(a.max()) + 1 if a.size else 1
+    return max(int(num_classes), 1)
+
+
+def _knn_vote_summary(K, idx, dist, q_labels, g_labels, n_classes, weights, temperature, top_n):
+    """one vote launch on a [Nq, k] table and the accuracies of its best classes as ONE device tensor:
+    [len(top_n) top-n accuracies, the mean per-class accuracy] in float64.  A class counts among a query's n best only with a
+    positive score: classes nobody voted for fill the tail of the ranking in class order and say nothing."""
+    from .neighbors import WEIGHTS
+    n_top = max(top_n)
+    _, pred, score = K.vote(idx, dist, g_labels, n_classes, WEIGHTS[weights], temperature, n_top, False)
+    match = (pred.to(torch.int64) == q_labels[:, None]) & (score > 0)
+    Nq = idx.shape[0]
+    accs = [match[:, :n].any(dim=1).sum().to(torch.float64) / Nq for n in top_n]
+    # mean per-class accuracy of the top-1 prediction, over the classes that occur among the queries
+    ok = (q_labels >= 0) & (q_labels < n_classes)
+    ql = q_labels.clamp(0, n_classes - 1)
+    per_class_n = torch.bincount(ql[ok], minlength=n_classes).to(torch.float64)
+    per_class_hit = torch.bincount(ql[ok & match[:, 0]], minlength=n_classes).to(torch.float64)
+    present = per_class_n > 0
+    mean_class = (per_class_hit / per_class_n.clamp(min=1))[present].sum() / present.sum().clamp(min=1).to(torch.float64)
+    return torch.stack(accs + [mean_class])
+
+
+def knn_classify(x_embeddings, x_labels, y_embeddings=None, y_labels=None, k=20, weights='softmax', temperature=0.07, top_n=(1, 5),
+                 num_classes=None, dist_metric='cosine', *, precision="fp32", kernels=None):
+    """Weighted k-NN classification accuracy of the queries x against the gallery y (the k-NN monitor of InstDisc / MoCo / DINO with
+    weights='softmax'; sklearn's KNeighborsClassifier with 'uniform' / 'distance'): one top-k search, one slic_knn_vote launch, one
+    small read-back.  y_embeddings=None is the leave-one-out form on one set.  Labels are classes 0 .. num_classes - 1 (default:
+    max label + 1; gallery labels < 0, noise used as pseudo-labels, never vote).
+    -> {'top1': .., 'top5': .. (one per entry of top_n), 'mean_class_acc': .., 'n_queries': Nq}"""
+    from .neighbors import WEIGHTS, check_vote_sizes
+    _check_precision(precision)
+    if weights not in WEIGHTS:
+        raise ValueError("weights must be 'uniform', 'distance' or 'softmax', got {!r}".format(weights))
+    if dist_metric not in ('cosine', 'euclidean'):
+        raise ValueError("dist_metric must be 'cosine' or 'euclidean', not %r" % (dist_metric,))
+    top_n = [int(n) for n in top_n]
+    if not top_n or min(top_n) < 1:
+        raise ValueError("top_n must hold positive integers, got {!r}".format(top_n))
+    g_host = x_labels if y_labels is None else y_labels
+    n_classes = _class_count(g_host, num_classes)
+    check_vote_sizes("knn_classify", k, n_classes, max(top_n))
+    K = _knn_provider(kernels)
+    q_labels = K.labels(x_labels)
+    g_labels = q_labels if y_embeddings is None else K.labels(y_labels)
+    idx, dist = K.search(x_embeddings, y_embeddings, int(k), dist_metric, precision)
+    rec = K.read(_knn_vote_summary(K, idx, dist, q_labels, g_labels, n_classes, weights, temperature, top_n))
+    out = {"top%d" % n: float(rec[i]) for i, n in enumerate(top_n)}
+    out["mean_class_acc"] = float(rec[len(top_n)])
+    out["n_queries"] = int(idx.shape[0])
+    return out
+
+
+def _n_relevant(q_labels, g_labels, leave_one_out):
+    """n_rel [Nq] int32: how many gallery rows carry the query's label (minus the query itself in the leave-one-out form), from a
+    label histogram on the labels' own device"""
+    both, inverse = torch.unique(torch.cat((q_labels, g_labels)), sorted=True, return_inverse=True)
+    hist = torch.bincount(inverse[q_labels.shape[0]:], minlength=both.shape[0])
+    n_rel = hist[inverse[:q_labels.shape[0]]]
+    return (n_rel - 1 if leave_one_out else n_rel).to(torch.int32)
+
+
+def retrieval_metrics(x_embeddings, x_labels, y_embeddings=None, y_labels=None, ks=(1, 5, 10, 20, 50), dist_metric='cosine', *,
+                      precision="fp32", kernels=None):
+    """Ranked retrieval quality of the queries x against the gallery y on the exact top-max(ks) lists: precision@k, recall@k, mAP@k
+    (AP@k normalised by min(relevant rows, k)) and the mean reciprocal rank (0 for a query without a hit in the list).  One search,
+    slic_retrieval_ranked, one small read-back; y_embeddings=None is the leave-one-out form.  Queries without any relevant gallery row
+    stay out of the recall and mAP means (n_with_relevant counts the others); precision and mrr average over all queries.
+    -> {'precision': {k: ..}, 'recall': {k: ..}, 'map': {k: ..}, 'mrr': .., 'n_with_relevant': ..}"""
+    from .neighbors import MAX_CUTS, MAX_K
+    _check_precision(precision)
+    if dist_metric not in ('cosine', 'euclidean'):
+        raise ValueError("dist_metric must be 'cosine' or 'euclidean', not %r" % (dist_metric,))
+    ks = [int(v) for v in ks]
+    if not 1 <= len(ks) <= MAX_CUTS or ks != sorted(ks) or ks[0] < 1:
+        raise ValueError("ks must be 1 .. {} ascending positive cut-offs, got {!r}".format(MAX_CUTS, ks))
+    if ks[-1] > MAX_K:
+        raise ValueError("retrieval_metrics: ks up to {} are beyond the {} of the exact top-k search (full-ranking mAP needs every "
+                         "relevant row's rank: DESIGN.md section 7j)".format(ks[-1], MAX_K))
+    K = _knn_provider(kernels)
+    q_labels = K.labels(x_labels)
+    loo = y_embeddings is None
+    g_labels = q_labels if loo else K.labels(y_labels)
+    idx, _ = K.search(x_embeddings, y_embeddings, ks[-1], dist_metric, precision)
+    _, _, record = K.ranked(idx, q_labels, g_labels, _n_relevant(q_labels, g_labels, loo), ks)
+    rec = K.read(record)
+    out = {"precision": {}, "recall": {}, "map": {}}
+    for i, k in enumerate(ks):
+        out["precision"][k], out["recall"][k], out["map"][k] = (float(v) for v in rec[3 * i:3 * i + 3])
+    out["mrr"] = float(rec[3 * len(ks)])
+    out["n_with_relevant"] = int(round(float(rec[3 * len(ks) + 1])))
+    return out
+
+
+def _knn_monitor(cfg, kernels, test_embeddings, test_labels, train_embeddings, train_labels):
+    """k_nearest_embeddings with VAL.KNN_K > 0: ONE search at max(20, KNN_K) serves both the four retrieval accuracies (the top-20
+    prefix of an exact sorted list is the exact top-20) and the k-NN classification monitor on its first KNN_K columns."""
+    knn_k = int(cfg.VAL.KNN_K)
+    weights = getattr(cfg.VAL, "KNN_WEIGHTS", "softmax")
+    temperature = float(getattr(cfg.VAL, "KNN_T", 0.07))
+    top_ks = [1, 5, 10, 20]
+    K = _knn_provider(kernels)
+    q_labels, g_labels = K.labels(test_labels), K.labels(train_labels)
+    n_classes = _class_count(train_labels, None)
+    from .neighbors import check_vote_sizes
+    check_vote_sizes("k_nearest_embeddings (VAL.KNN_K)", knn_k, n_classes, 5)
+    idx, dist = K.search(test_embeddings, train_embeddings, max(top_ks[-1], knn_k), cfg.LOSS.DIST_METRIC)
+    head = idx[:, :top_ks[-1]].contiguous()
+    hits = _label_hits(head, q_labels, g_labels, top_ks) if kernels is None else kernels.label_hits(head, q_labels, g_labels, top_ks)
+    acc = hits.cpu().numpy().astype(np.float64) / idx.shape[0]
+    knn = K.read(_knn_vote_summary(K, idx[:, :knn_k].contiguous(), dist[:, :knn_k].contiguous(), q_labels, g_labels, n_classes,
+                                   weights, temperature, [1, 5]))
+    return acc, (float(knn[0]), float(knn[1])), (knn_k, weights)
+
+
 def k_nearest_embeddings(args, model, cuda, device, train_loader, test_loader, train_data, val_data, cfg, test_split='val',
                          plot=True, epoch=None, is_master_proc=True, evaluate_output=None, num_exemplar=None, service=None,
                          load_pkl=False, out_filename='global_retrieval_acc', *, kernels=None):
@@ -308,9 +440,14 @@ def k_nearest_embeddings(args, model, cuda, device, train_loader, test_loader, t
                                                                   is_master_proc=is_master_proc, load_pkl=load_pkl)
     acc = []
     print('Computing top1/5/10/20 Acc...')
+    knn_k = int(getattr(getattr(cfg, "VAL", None), "KNN_K", 0) or 0)       # opt-in: absent or 0 leaves every step below as it was
+    knn = None
     if (is_master_proc):
-        acc = topk_acc_device(test_embeddings, test_labels, train_embeddings, train_labels, dist_metric=cfg.LOSS.DIST_METRIC,
-                              kernels=kernels)
+        if knn_k > 0:
+            acc, knn, knn_how = _knn_monitor(cfg, kernels, test_embeddings, test_labels, train_embeddings, train_labels)
+        else:
+            acc = topk_acc_device(test_embeddings, test_labels, train_embeddings, train_labels, dist_metric=cfg.LOSS.DIST_METRIC,
+                                  kernels=kernels)
         if epoch is not None:
             # the reference's format string has two placeholders for its four arguments: the file holds top-1 and top-5
             to_write = 'epoch:{} {:.2f} {:.2f}'.format(epoch, 100.*acc[0], 100.*acc[1], 100.*acc[2], 100.*acc[3])
@@ -318,6 +455,11 @@ def k_nearest_embeddings(args, model, cuda, device, train_loader, test_loader, t
             from .online_train import _append_log
             _append_log(cfg, '{}.txt'.format(out_filename), to_write)
         print('Top1 Acc: {:.2f}%, Top5 Acc: {:.2f}%, Top10 Acc: {:.2f}%, Top20 Acc: {:.2f}%'.format(100.*acc[0], 100.*acc[1], 100.*acc[2], 100.*acc[3]))
+        if knn is not None:
+            print('kNN (k={}, {}) Top1 Acc: {:.2f}%, Top5 Acc: {:.2f}%'.format(knn_how[0], knn_how[1], 100.*knn[0], 100.*knn[1]))
+            if epoch is not None:
+                from .online_train import _append_log
+                _append_log(cfg, 'knn_acc.txt', 'epoch:{} {:.2f} {:.2f}\n'.format(epoch, 100.*knn[0], 100.*knn[1]))
     return acc
 
 
