@@ -927,32 +927,6 @@ __global__ void pack_w_fwd_runs(const float* __restrict__ W, int N, int C, int n
   const int tap = run * PPR + px;
   Wp[e] = (px < PPR && tap < ntaps) ? W[((int64_t)n * C + c) * ntaps + tap] : 0.f;
 }
-// data gradient:  Wd[c][tap*N + n] = W[n][c][tap]   (rows = input channels, Cs rows, zero padded).
-// Workgroup = (32 output channels n, CB input channels c): reads CB*ntaps contiguous floats per n, writes 32 consecutive n.
-__global__ __launch_bounds__(256) void pack_w_dgrad(const float* __restrict__ W, int N, int C, int ntaps, int Cs, int Kd,
-                                                    int CB, float* __restrict__ Wd) {
-  extern __shared__ float pk_lds[];                        // [32][ld]
-  const int n0 = blockIdx.x * 32, c0 = blockIdx.y * CB, t = threadIdx.x;
-  const int run = CB * ntaps;
-  const int ld = run | 1;
-  const int cw = min(CB, C - c0);                          // real channels (<= 0: padding rows)
-  const int cbw = min(CB, Cs - c0);
-  const int nw = min(32, N - n0);
-  const int rw = cw > 0 ? cw * ntaps : 0;
-  for (int e = t; e < nw * rw; e += 256) {
-    const int nn = e / rw, r = e - nn * rw;
-    pk_lds[nn * ld + r] = W[((int64_t)(n0 + nn) * C + c0) * ntaps + r];
-  }
-  __syncthreads();
-  for (int e = t; e < cbw * ntaps * 32; e += 256) {
-    const int nn = e & 31, q = e >> 5;                     // q = cc * ntaps + tap
-    const int cc = q / ntaps, tap = q - cc * ntaps;
-    if (nn < nw) Wd[(int64_t)(c0 + cc) * Kd + tap * N + n0 + nn] = cc < cw ? pk_lds[nn * ld + q] : 0.f;
-  }
-  if (blockIdx.x == 0)
-    for (int cc = 0; cc < cbw; ++cc)
-      for (int k = ntaps * N + t; k < Kd; k += 256) Wd[(int64_t)(c0 + cc) * Kd + k] = 0.f;
-}
 
 // ---- layout conversion ------------------------------------------------------------------------
 // NCDHW [B, C, S] -> NDHWC [B, S, Cp] (S = T*H*W, channels zero-padded to Cp)
