@@ -906,6 +906,38 @@ int slic_silhouette(const float* X, int64_t N, int D, int64_t ldx, const int32_t
                     int32_t ignore_label, int64_t Kmax, float* out_s, float* out_a, float* out_b, int32_t* out_nearest,
                     double* record, double* cluster_mean, int32_t* cluster_label, void* workspace, void* stream);
 
+/* Pair statistics: the distribution of the pairwise cosine distances of rows X [Nx, D] fp32 (row stride ldx elements), split into
+ * the pairs whose rows share a label (group 1, "same") and all other pairs (group 0, "diff"), in one streamed pass over the
+ * 128 x 128 tiles of the similarity matrix (the walk of slic_dbscan_cosine's count pass); the matrix is never written.
+ *   Y == NULL: X against itself, every pair i < j exactly once, a row never with itself (Ny, ldy, ly are not read).
+ *   Y != NULL: every pair (q, g) of a row of X and a row of Y [Ny, D] (row stride ldy).
+ * Rules:
+ *   1. Operands.  inv_i = 1 / ||x_i|| in float64 (k ascending; 0 for a zero row); the operand row is fp32(x_i * inv_i), zero-padded
+ *      to D % 8 == 0: slic_dbscan_cosine's preparation, shared in code.  A zero row is therefore at d = 1 from every row, as in
+ *      slic_cosine_topk.
+ *   2. Score.  s = the fp32 dot product of two operand rows (v_mfma_f32_32x32x2_f32, the MFMA ring's k order);
+ *      d = fminf(fmaxf(1.0f - s, 0.0f), 2.0f).
+ *   3. Bin.  bin = min(bins - 1, (int)(d * (bins / 2))); bins is a power of two in 8 .. SLIC_PAIR_STATS_MAX_BINS, so the product is
+ *      exact: bin b holds b * 2 / bins <= d < (b + 1) * 2 / bins, and d = 2 falls into the last bin.
+ *   4. Group.  1 iff both rows carry a label (lx and, with Y, ly are not NULL; int32, unit stride) and the labels are equal, else 0.
+ *      Without labels every pair is in group 0.  has_ignore != 0: a row labelled ignore_label takes part in no pair.
+ * Outputs (device): hist uint64 [2][bins], hist[g][bin] = pairs of group g in the bin; record (SLIC_PAIR_STATS_RECORD doubles):
+ *   n_diff, n_same, sum d (diff, same), sum d^2 (diff, same), sum e (diff, same), status (0),   e = expf(-tt * d), tt = (float)(2 t)
+ * (|x^_i - x^_j|^2 = 2 d, so log(sum e / n) is the uniformity of Wang & Isola at temperature t).  d^2 is the float64 square of d.
+ * The counts come by integer atomics.  The float64 sums use no floating-point atomic: a lane adds its scores in the tile walk's
+ * order, a workgroup folds its lanes by halving, the workgroups' partial sums lie in the workspace and one workgroup adds them in a
+ * fixed order: two calls on the same input give the same bits in hist and record.  The call never synchronises with the host.
+ * Limits: 1 <= Nx, Ny <= SLIC_PAIR_STATS_MAX_N (Nx = 1 in the self form is valid and counts nothing), 1 <= D <= 512, the padded
+ * rows of one side below 4 GiB, 0 < t <= 1e30, row strides in D .. 2^31 - 1; SLIC_EINVAL beyond.  The workspace query takes Ny = 0
+ * for the self form; the workspace holds the operand rows, 4 N Dp bytes per side, and 48 bytes per 128 x 2048 block of pairs. */
+#define SLIC_PAIR_STATS_MAX_N ((int64_t)1 << 20)
+#define SLIC_PAIR_STATS_MAX_BINS 4096
+#define SLIC_PAIR_STATS_RECORD 9
+size_t slic_pair_stats_workspace_bytes(int64_t Nx, int64_t Ny, int D, int bins);     /* 0 for sizes slic_pair_stats rejects */
+int slic_pair_stats(const float* X, int64_t Nx, int64_t ldx, const int32_t* lx, const float* Y, int64_t Ny, int64_t ldy,
+                    const int32_t* ly, int D, int bins, int has_ignore, int32_t ignore_label, double t, uint64_t* hist,
+                    double* record, void* workspace, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Memory-bank NCE (loss/NCE_loss.py:26-88 NCEAverage, :341-352 NCESoftmaxLoss): gather + dot + /T without
  * materialising the gathered rows, its backward wrt the features, the momentum bank update, and the

@@ -180,6 +180,9 @@ SIGNATURES = {
     # silhouette coefficient (cosine / sqeuclidean) from per-cluster row sums
     "slic_silhouette_workspace_bytes": (c_size_t, [L, I, L]),
     "slic_silhouette": (I, [P, L, I, L, P, I, I, ctypes.c_int32, L, P, P, P, P, P, P, P, P, P]),
+    # pair statistics: same / different-label histograms of the pairwise cosine distances
+    "slic_pair_stats_workspace_bytes": (c_size_t, [L, L, I, I]),
+    "slic_pair_stats": (I, [P, L, L, P, P, L, L, P, I, I, I, ctypes.c_int32, Dbl, P, P, P, P]),
     # memory-bank NCE
     "slic_nce_scores_fwd": (I, [P, P, P, I, I, I, F, P, P, P]),
     "slic_nce_scores_bwd": (I, [P, P, P, I, I, I, F, P, P]),

@@ -38,6 +38,10 @@ def __getattr__(name):
     # constant is the only copy (slic_cosine_topk_bf16_eps), read when somebody asks for it.
     if name == "TOPK_BF16_EPS":
         return float(_lib.load().slic_cosine_topk_bf16_eps())
+    # the pair statistics (pairstats.py) are reachable from here, imported when somebody asks for them
+    if name in ("pair_statistics", "view_statistics", "separation", "HipPairStatsKernels"):
+        from . import pairstats
+        return getattr(pairstats, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
 
 

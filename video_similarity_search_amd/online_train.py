@@ -332,8 +332,20 @@ def _silhouette_lines(cfg, epoch, embeddings, cluster_labels, kernels):
     _append_log(cfg, 'silhouettes.txt', 'epoch:{} {:.3f}\n'.format(epoch, sil))
 
 
+def _pair_stats_lines(cfg, epoch, embeddings, true_labels, bins, kernels):
+    """the opt-in pair statistics of the cluster step (cfg.ITERCLUSTER.PAIR_STATS = bins): one print, one line in pair_stats.txt"""
+    from .pairstats import pair_statistics, separation
+    st = pair_statistics(embeddings, true_labels, bins=bins, ignore_label=-1, kernels=kernels)
+    sep = separation(st, precision=(0.9,))
+    d90 = sep['d_at_precision'][0.9]
+    line = 'intra {:.3f} +- {:.3f} inter {:.3f} +- {:.3f} AUC {:.3f} d(precision 0.9) {}'.format(
+        st['mean_same'], st['std_same'], st['mean_diff'], st['std_diff'], sep['auc'], 'none' if d90 is None else '{:.4f}'.format(d90))
+    print('Pair distances (cosine) under the true labels: ' + line)
+    _append_log(cfg, 'pair_stats.txt', 'epoch:{} {}\n'.format(epoch, line))
+
+
 def iterative_cluster_step(args, cfg, encoder, eval_train_loader, epoch, cuda=True, device=None, is_master_proc=True,
-                           kmeans_kernels=None, metrics_kernels=None, silhouette_kernels=None):
+                           kmeans_kernels=None, metrics_kernels=None, silhouette_kernels=None, pairstats_kernels=None):
     """online_train.py:605-662: embeddings of the whole train set -> fit_cluster -> NMI/AMI logs -> vid_clusters.txt in
     the dataset's unshuffled order -> barrier.
 
@@ -354,7 +366,11 @@ def iterative_cluster_step(args, cfg, encoder, eval_train_loader, epoch, cuda=Tr
     cfg.ITERCLUSTER.SILHOUETTE (default off; the gathered route only — with the sharded route it raises NotImplementedError before
     any collective): after the NMI / AMI lines, the cosine silhouette of the assignments (clustering/metrics.py, one device call;
     DBSCAN's -1 rows ignored) is printed and appended to silhouettes.txt.  It needs a device or `silhouette_kernels`; an undefined
-    score (fewer than 2 clusters, or one per row) prints one line and training goes on."""
+    score (fewer than 2 clusters, or one per row) prints one line and training goes on.
+    cfg.ITERCLUSTER.PAIR_STATS = bins (absent or 0: off; the gathered route only, NotImplementedError before any collective with the
+    sharded one): after those lines, the same-label / different-label histogram of the pairwise cosine distances under the TRUE labels
+    (pairstats.py, one device call; rows labelled -1 ignored): intra- and inter-class mean +- std, the AUC and the distance below which
+    0.9 of the pairs share a label are printed and appended to pair_stats.txt.  It needs a device or `pairstats_kernels`."""
     import numpy as np
     from .clustering.cluster_masks import fit_cluster
     from .evaluate import get_embeddings_and_labels
@@ -363,6 +379,10 @@ def iterative_cluster_step(args, cfg, encoder, eval_train_loader, epoch, cuda=Tr
     want_silhouette = bool(getattr(cfg.ITERCLUSTER, "SILHOUETTE", False))
     if want_silhouette and sharded:
         raise NotImplementedError("cfg.ITERCLUSTER.SILHOUETTE is not built for the row-sharded cluster step: every rank holds only "
+                                  "its rows; set ITERCLUSTER.SHARDED = False or leave the flag off")
+    pair_bins = int(getattr(cfg.ITERCLUSTER, "PAIR_STATS", 0) or 0)
+    if pair_bins and sharded:
+        raise NotImplementedError("cfg.ITERCLUSTER.PAIR_STATS is not built for the row-sharded cluster step: every rank holds only "
                                   "its rows; set ITERCLUSTER.SHARDED = False or leave the flag off")
     if is_master_proc:
         print('\n=> Computing embeddings')
@@ -455,6 +475,8 @@ def iterative_cluster_step(args, cfg, encoder, eval_train_loader, epoch, cuda=Tr
                 pass
         if want_silhouette:
             _silhouette_lines(cfg, epoch, embeddings, cluster_labels, silhouette_kernels)
+        if pair_bins:
+            _pair_stats_lines(cfg, epoch, embeddings, true_labels, pair_bins, pairstats_kernels)
         # one label per line, unshuffled dataset order (online_train.py:654-657); a slot the loader never produced is
         # written as the reference writes it ('None'), a DBSCAN noise row as its label, -1
         produced = np.zeros(n_data, dtype=bool)
